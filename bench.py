@@ -6,7 +6,18 @@ GPU, synthetic random actions generated on device (counter RNG keyed by global l
 gym TimeLimit + done -> on-device auto-reset inside the timed loop (as SB3's VecEnv would).
 A "step" is one k_step launch advancing every lane of every rank by one env step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env ID] [--lanes L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env ID] [--lanes L] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, the K timed
+steps (one event pair around them for kernel_ms), the lane checks of the timed window (two small
+reads; a figure over faulted or non-finite lanes is no figure, exit 3), and the JSON line.
+--dump-outputs DIR then writes what the last timed step returned (DIR/<name>.npy, float32); the
+inputs are a function of the arguments alone (counter RNG keyed by seed, lane and step), so two
+builds run with the same arguments can be compared array for array.
+--full adds every measurement that takes runs of its own: the CPU baseline (cpu_baseline), the later
+window, the whole episode, the multi-step launches and the gym-style single env (diagnostics);
+their options (--later-window, --episode, --multi-step, --single-env, --no-cpu-baseline) select
+among them under --full and are ignored without it.
 
 For N > 1 launch one process per GPU (torch.distributed.run); lanes shard contiguously
 (rank r owns global lanes [r*L, (r+1)*L)), per-lane trajectories are independent of N, and
@@ -241,6 +252,35 @@ def load_traffic(env_id: int, lanes: int):
     return None
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: all files of one run together stay under 64 MB
+
+
+def snapshot_outputs(tensors: dict) -> dict:
+    """Host float32 copies (float64 stays float64) of the timed path's output tensors (name -> array whose first axis is the
+    lane), taken before any later diagnostic steps the same buffers.  When the copies together
+    would pass DUMP_LIMIT_BYTES each array keeps a fixed sample of its lanes (seeded, sorted, the
+    same share of every array), stored beside it as `<name>_lanes`."""
+    import torch
+    total = sum(8 * t.numel() + 8 * int(t.shape[0]) for t in tensors.values())   # as if all were float64
+    share = min(1.0, DUMP_LIMIT_BYTES / total)
+    out = {}
+    for name, t in tensors.items():
+        rows = int(t.shape[0])
+        if share < 1.0:
+            keep = np.sort(np.random.RandomState(0).choice(rows, size=max(1, int(rows * share)), replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+            out[name + "_lanes"] = keep.astype(np.float64)
+        a = t.detach().to("cpu").numpy()
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    return out
+
+
+def write_outputs(directory: str, arrays: dict) -> None:
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,7 +302,14 @@ def main():
                          "--nproc-per-node 1)")
     ap.add_argument("--dump-gather", default="",
                     help="N>1 check: rank 0 saves every timed step's gathered (obs | reward | done) rows to this .npy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned (obs, reward, done, "
+                         "truncated, status; the normalised and gathered arrays when those paths run) as DIR/<name>.npy, "
+                         "float32, under 64 MB in all (a fixed seeded sample of the lanes beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the diagnostics below "
+                         "(later window, whole episode, multi-step launches, single env); without it they are off")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--schedule", type=int, default=-1, help="mrp_set_schedule mode: 0 lane order, 1 costliest-first dispatch, 2 cost priority, 3 both; default: the library's per-env choice (mrp_create)")
     ap.add_argument("--time-every", type=int, default=0,
                     help="0 (default): one HIP event pair around all K timed launches on the kernel's stream, kernel_ms = "
@@ -282,6 +329,9 @@ def main():
     ap.add_argument("--vecnormalize", action="store_true",
                     help="also run SB3 VecNormalize + Monitor statistics on the device every step (train.py:68,80-82)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: nothing beyond the timed steps
+        args.no_cpu_baseline = True
+        args.single_env = args.later_window = args.episode = args.multi_step = 0
     if args.same_device and args.dist_backend != "gloo":
         ap.error("--same-device needs --dist-backend gloo (RCCL refuses two ranks on one device)")
     if args.same_device and int(os.environ.get("WORLD_SIZE", "1")) < 2:
@@ -396,6 +446,14 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        last = {"obs": obs, "reward": rew, "done": done, "truncated": trunc, "status": status}
+        if norm is not None:
+            last.update(norm_obs=nobs, norm_reward=nrew, terminal_obs=term, norm_terminal_obs=nterm,
+                        episode_return=epr, episode_length=epl)
+        if gather is not None:
+            last["gathered"] = gather.full
+        write_outputs(args.dump_outputs, snapshot_outputs(last))
     ev = [x for x in ev if x is not None]
     kts = np.array([s.elapsed_time(e) for s, e in ev]) if ev else None
     if alone and TE == 0:
@@ -522,7 +580,7 @@ def main():
                        "collective": None if not distributed or args.no_gather else
                                      (args.dist_backend + (" (host-staged)" if host_coll else " (RCCL)")
                                       + (" forced at world size 1" if world == 1 else "")),
-                       "dump_gather": bool(dumps is not None),
+                       "dump_gather": bool(dumps is not None), "full": bool(args.full),
                        "devices": 1 if (world == 1 or args.same_device) else world,
                        "vecnormalize": bool(args.vecnormalize),
                        "dispatch": ("lane order" if args.schedule == 0 else f"mrp_set_schedule({args.schedule})") if args.schedule >= 0

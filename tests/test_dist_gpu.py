@@ -58,6 +58,35 @@ def _one_batch_rows(env_id, lanes, W, K):
 
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_last_timed_step(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, measures nothing else (no CPU
+    baseline, no diagnostic windows), and --dump-outputs writes the last timed step's outputs as
+    float32 .npy files: bit for bit what one process stepping the same batch returns at step W + K."""
+    W, K, lanes = 2, 5, 192
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--env", "0", "--lanes", str(lanes),
+           "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["warmup"] == W and line["checks"]["ok"] and not line["config"]["full"]
+    assert line["diagnostics"]["counters"]["timed_window"]["steps"] == lanes * K
+    assert line["value"] == pytest.approx(lanes * K / (line["ms_per_step"] * K * 1e-3), rel=1e-6)
+    assert "cpu_baseline" not in line
+    assert all(line["diagnostics"][k] is None for k in ("later_window", "whole_episode", "multi_step_launch",
+                                                        "single_env_drop_in"))
+    got = {n: np.load(out / f"{n}.npy") for n in ("obs", "reward", "done", "truncated", "status")}
+    assert all(a.dtype == np.float32 and a.shape[0] == lanes for a in got.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64e6
+    exp = _one_batch_rows(0, lanes, W, K)[-1]
+    assert np.array_equal(got["obs"], exp[:, :-2])
+    assert np.array_equal(got["reward"], exp[:, -2]) and np.array_equal(got["done"], exp[:, -1])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
 def test_bench_rccl_gather_one_rank(tmp_path):
     """bench.py's distributed branch over RCCL on the box's one GPU: WORLD_SIZE 1 under
     torch.distributed.run, --dist-backend nccl --force-collective (dist.gather of the packed device

@@ -15,5 +15,6 @@ for k in "${!ENVS[@]}"; do
   python3 tools/kt_window.py "$(find $D/kt -name '*kernel_trace.csv' -print -quit)" ${WARMUP:-10} ${STEPS:-100} \
       profiles/${R}_${k}_bench_under_rocprof.json > profiles/${R}_${k}_kernel_window.json
 done
-grep -h '"metric"' gpurun_out/bench_default.log > profiles/${R}_bench_default.json
-grep -h '"metric"' gpurun_out/bench_driver.log > profiles/${R}_bench_driver_window.json
+OUT=${OUT:-bench_out}   # tools/profile_all.sh's bench logs
+grep -h '"metric"' "$OUT/bench_default.log" > profiles/${R}_bench_default.json
+grep -h '"metric"' "$OUT/bench_driver.log" > profiles/${R}_bench_driver_window.json

@@ -12,7 +12,7 @@ for r in 0 1; do
     [ "$rest" != "$lib" ] && extra=$(echo "${rest#*:}" | tr ',' ' ')
     MRP_LIB=$lib timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --single-env 0 --later-window 0 --episode 0 --multi-step 0 $extra > "$OUT/drv_${n}_$r.log" 2>&1 \
       || { echo "bench failed ($n)"; tail -20 "$OUT/drv_${n}_$r.log"; exit 1; }
-    MRP_LIB=$lib timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --single-env 0 --later-window 0 --episode 1 --multi-step 0 $extra > "$OUT/def_${n}_$r.log" 2>&1 \
+    MRP_LIB=$lib timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --single-env 0 --later-window 0 --episode 1 --multi-step 0 $extra > "$OUT/def_${n}_$r.log" 2>&1 \
       || { echo "bench failed ($n)"; tail -20 "$OUT/def_${n}_$r.log"; exit 1; }
     python - "$OUT/drv_${n}_$r.log" "$OUT/def_${n}_$r.log" "$n" "$r" <<'PY'
 import json, sys
