@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .spawn import ENV_VERSION
+from .spawn import ENV_IDS, ENV_VERSION  # noqa: F401  (ENV_IDS: the package's public name table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmrp.so")
@@ -22,23 +22,6 @@ STATUS_KIND_MASK, STATUS_NONFINITE, STATUS_FAULT = 0x3F, 0x40, 0x80   # include/
 COUNTER_NAMES = ("steps", "resets", "toi_events", "position_iterations", "touching_contacts", "nonfinite_steps",
                  "faulted_lanes")
 
-ENV_IDS = {
-    "MultiRobotPuzzle-v0": 0,
-    "MultiRobotPuzzleHeavy-v0": 1,
-    "MultiRobotPuzzle-v2": 2,
-    "MultiRobotPuzzleHeavy-v2": 3,
-    "MultiRobotPuzzleHeavy-v2-3block": 4,
-    "MultiRobotPuzzle-v3": 5,
-    "MultiRobotPuzzle-v3-heavy": 6,      # RobotPuzzleBase(heavy=True) (tests/test_env.py:12)
-    # MultiRobotPuzzle2 / MultiRobotPuzzleHeavy2(num_agents=N) (multi_robot_puzzle_02.py:139)
-    "MultiRobotPuzzle-v2-agents1": 7, "MultiRobotPuzzle-v2-agents3": 8, "MultiRobotPuzzle-v2-agents4": 9,
-    "MultiRobotPuzzle-v2-agents5": 10, "MultiRobotPuzzleHeavy-v2-agents1": 11, "MultiRobotPuzzleHeavy-v2-agents3": 12,
-    "MultiRobotPuzzleHeavy-v2-agents4": 13, "MultiRobotPuzzleHeavy-v2-agents5": 14,
-    # RobotPuzzleBase(num_agents=N[, heavy=True]) (core.py:86-106)
-    "MultiRobotPuzzle-v3-agents1": 15, "MultiRobotPuzzle-v3-agents3": 16, "MultiRobotPuzzle-v3-agents4": 17,
-    "MultiRobotPuzzle-v3-agents5": 18, "MultiRobotPuzzle-v3-heavy-agents1": 19, "MultiRobotPuzzle-v3-heavy-agents3": 20,
-    "MultiRobotPuzzle-v3-heavy-agents4": 21, "MultiRobotPuzzle-v3-heavy-agents5": 22,
-}
 MAXF = 24   # csrc/mrp_config.h: fixtures per env (mrp_shapes fills MAXF rows)
 
 # every symbol include/mrp.h declares (tests/test_abi.py checks the .so exports all of them)

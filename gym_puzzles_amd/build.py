@@ -4,12 +4,14 @@ Numerics flags are part of the contract: -ffp-contract=off (no FMA contraction, 
 expressions round exactly like the box2d-py engine), no fast-math, f32 denormals kept,
 correctly rounded f32 divide/sqrt.
 
-Each env id's lane kernels are their own translation unit (csrc/mrp_env<E>.hip), so the units
-compile in parallel and are linked into one shared library.
+Each env id's lane kernels are their own translation unit (csrc/mrp_unit.hip compiled with
+-DMRP_ENV=<id>, one per row of the registry in csrc/mrp_config.h), so the units compile in parallel
+and are linked into one shared library.
 """
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -17,12 +19,19 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmrp.so")
-N_ENVS = 23   # csrc/mrp_config.h N_ENVS: one translation unit per env id
-SOURCES = ([os.path.join(CSRC, "mrp_kernels.hip"), os.path.join(CSRC, "mrp_tables.cpp"), os.path.join(CSRC, "mrp_norm.hip")]
-           + [os.path.join(CSRC, f"mrp_env{e}.hip") for e in range(N_ENVS)])
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h",
-                                                  "mrp_ops.h", "mrp_lane.h", "mrp_render.h")] + [
-    os.path.join(HERE, "..", "include", "mrp.h"), os.path.abspath(__file__)]
+with open(os.path.join(CSRC, "mrp_config.h")) as _f:   # the rows of MRP_ENV_LIST: one translation unit per env id
+    N_ENVS = len(re.findall(r"^\s*X\(\d+,", _f.read(), re.M))
+# (source in csrc/, object name, env id of an env unit or None): the shared units, then one object per id
+SOURCES = ([(f, f + ".o", None) for f in ("mrp_kernels.hip", "mrp_tables.cpp", "mrp_norm.hip")]
+           + [("mrp_unit.hip", f"mrp_env{e}.o", e) for e in range(N_ENVS)])
+HEADERS = ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h", "mrp_ops.h", "mrp_lane.h", "mrp_render.h")
+
+
+def deps(csrc: str = CSRC) -> list[str]:
+    return [os.path.join(csrc, f) for f in sorted({s for s, _, _ in SOURCES}) + list(HEADERS)] + [
+        os.path.join(HERE, "..", "include", "mrp.h"), os.path.abspath(__file__)]
+
+
 # Per-unit flags.  The 3-block config (env 4, islands of 5-8 contacts) keeps its lanes-path sweep /
 # pass loops as functions of their own, scheduled for ILP: the machine scheduler then drops the
 # lanes-path update's s_nop wait states from about 40 to 17, +5.7 % env-steps/s in the driver window
@@ -87,9 +96,10 @@ _BFREE_LANES = ["-DMRP_VEL_BFREE=1", "-DMRP_VEL_BFREE_LANES=1"]
 # v0's steady state lost 7 % (profiles/r6_waves_ab.txt).  Round 3 had chosen 3 waves on the driver window
 # alone (level) and the spills' traffic.
 _W4 = ["-DMRP_STEP_WAVES_PER_EU=4"]
-UNIT_FLAGS = {"mrp_env0.hip": _LANES_PAIRS + _ITER_ILP + _FRESH + _BFREE_LANES + _W4, "mrp_env1.hip": _MAX_ILP,
-              "mrp_env2.hip": _GRANULES + _MAX_ILP + _BFREE, "mrp_env4.hip": _ILP_LOOPS + _BFREE,
-              "mrp_env5.hip": _LANES_PAIRS + _ITER_ILP + _FRESH + _BFREE_LANES + _W4}
+# env id -> that unit's flags; an id without an entry is compiled with FLAGS alone
+UNIT_FLAGS = {0: _LANES_PAIRS + _ITER_ILP + _FRESH + _BFREE_LANES + _W4, 1: _MAX_ILP,
+              2: _GRANULES + _MAX_ILP + _BFREE, 4: _ILP_LOOPS + _BFREE,
+              5: _LANES_PAIRS + _ITER_ILP + _FRESH + _BFREE_LANES + _W4}
 # -fno-slp-vectorize: the serial solver chains are latency-bound; packing pairs of f32 ops into
 # v_pk_* costs operand-shuffling moves on the dependency chain (measured +2-3 % env-steps/s off)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
@@ -108,36 +118,38 @@ def up_to_date() -> bool:
     if not os.path.exists(OUT):
         return False
     t = os.path.getmtime(OUT)
-    return all(os.path.getmtime(d) <= t for d in DEPS if os.path.exists(d))
+    return all(os.path.getmtime(d) <= t for d in deps() if os.path.exists(d))
 
 
 def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=(), jobs: int | None = None,
-          only_envs=None) -> str:
+          only_envs=None, csrc: str = CSRC) -> str:
     """Build libmrp.so (or a diagnostic variant with extra -D defines into ``out``).
 
     ``only_envs`` (A/B libraries): compile only those env units (plus the small shared units) and link
     the other env units' objects of the default build, which must exist; each env unit is
-    self-contained, so the variant differs from the default library only in the listed envs."""
+    self-contained, so the variant differs from the default library only in the listed envs.
+    ``csrc`` (tools/patch_variant.py): compile from a patched copy of the sources."""
     if not force and out == OUT and up_to_date():
         return out
     objdir = os.path.join(HERE, "build", os.path.basename(out) + ".obj")
     os.makedirs(objdir, exist_ok=True)
     dflags = [f"-D{d}" for d in defines]
-    objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in SOURCES]
+    srcs = [os.path.join(csrc, s) for s, _, _ in SOURCES]
+    objs = [os.path.join(objdir, o) for _, o, _ in SOURCES]
     todo = list(range(len(SOURCES)))
+    dep_files = deps(csrc)
     if only_envs is not None:
         assert out != OUT, "only_envs builds a variant library, never the default one"
-        keep = {f"mrp_env{e}.hip" for e in only_envs}
         base = os.path.join(HERE, "build", os.path.basename(OUT) + ".obj")
-        todo = [i for i, s in enumerate(SOURCES) if "mrp_env" not in s or os.path.basename(s) in keep]
+        todo = [i for i, (_, _, e) in enumerate(SOURCES) if e is None or e in only_envs]
         # the reused objects must have been compiled from the current sources and headers: an env
         # unit built before a shared header changed would mix two layouts in one A/B library
         # (MRP_ALLOW_STALE_UNITS=1 accepts it for an A/B of the listed envs when the edit leaves the
         # LaneState / EnvOps layout unchanged; mrp_create still checks each unit's compiled dims)
-        newest_dep = max(os.path.getmtime(d) for d in DEPS if os.path.exists(d) and d.endswith((".h", ".hip", ".cpp")))
-        for i, s in enumerate(SOURCES):
+        newest_dep = max(os.path.getmtime(d) for d in dep_files if os.path.exists(d) and d.endswith((".h", ".hip", ".cpp")))
+        for i, (_, o, _) in enumerate(SOURCES):
             if i not in todo:
-                objs[i] = os.path.join(base, os.path.basename(s) + ".o")
+                objs[i] = os.path.join(base, o)
                 if not os.path.exists(objs[i]):
                     raise FileNotFoundError(f"{objs[i]}: build the default library first")
                 if os.path.getmtime(objs[i]) < newest_dep and not os.environ.get("MRP_ALLOW_STALE_UNITS"):
@@ -147,12 +159,13 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
     # A/B only: extra compiler flags for a variant library (never the default one)
     extra = os.environ.get("MRP_EXTRA_FLAGS", "").split() if out != OUT else []
 
-    headers = [d for d in DEPS if d.endswith(".h")]
+    headers = [d for d in dep_files if d.endswith(".h")]
     newest_header = max(os.path.getmtime(d) for d in headers if os.path.exists(d))
 
     def compile_one(i: int) -> None:
-        unit = UNIT_FLAGS.get(os.path.basename(SOURCES[i]), []) if not extra else []
-        cmd = [hipcc()] + FLAGS + unit + extra + dflags + ["-c", SOURCES[i], "-o", objs[i]]
+        env = SOURCES[i][2]
+        unit = [] if env is None else (UNIT_FLAGS.get(env, []) if not extra else []) + [f"-DMRP_ENV={env}"]
+        cmd = [hipcc()] + FLAGS + unit + extra + dflags + ["-c", srcs[i], "-o", objs[i]]
         # incremental: an object newer than its source and every header, built with the same command
         # line (recorded beside it), is kept; the env units include every header, so a header edit
         # rebuilds them all, while an edit of mrp_kernels.hip alone rebuilds that unit only
@@ -162,7 +175,7 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
             t = os.path.getmtime(objs[i])
             with open(stamp) as f:
                 same = f.read() == line
-            if same and t >= os.path.getmtime(SOURCES[i]) and t >= newest_header:
+            if same and t >= os.path.getmtime(srcs[i]) and t >= newest_header:
                 return
         if verbose:
             print(line, flush=True)
@@ -172,7 +185,7 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
 
     # slowest units first; each hipcc is single-threaded, so one job per core
     jobs = jobs or max(1, min(len(SOURCES), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", "16"))))
-    order = sorted(todo, key=lambda i: "mrp_env" not in SOURCES[i])
+    order = sorted(todo, key=lambda i: SOURCES[i][2] is None)
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(compile_one, order))
     cmd = [hipcc()] + FLAGS + ["-shared"] + objs + ["-o", out + ".tmp"]

@@ -1,5 +1,5 @@
 // mrp_config.h -- per-environment static tables (geometry, mass, spawn bounds) and the
-// compile-time dimensions of each registered MultiRobotPuzzle id.
+// registry of the MultiRobotPuzzle ids with their compile-time dimensions.
 //
 // Env ids follow include/mrp.h: 0 MultiRobotPuzzle-v0, 1 MultiRobotPuzzleHeavy-v0,
 // 2 MultiRobotPuzzle-v2, 3 MultiRobotPuzzleHeavy-v2, 4 Heavy-v2 with the build-defined
@@ -16,67 +16,83 @@ namespace mrp {
 // status byte flags next to the terminal kind (include/mrp.h MRP_STATUS_NONFINITE / MRP_STATUS_FAULT)
 constexpr int MRP_STATUS_NONFINITE_BIT = 0x40, MRP_STATUS_FAULT_BIT = 0x80;
 
+constexpr int BLOCK = 64;     // threads of a lane kernel's workgroup: one wave, so lanes of a block never wait on each other
 constexpr int MAX_POLY = 8;
 constexpr int MAXBODY = 10;   // bodies: blocks + agents + 4 walls (max over configs: 1 + 5 + 4)
 constexpr int MAXF = 24;      // fixtures (max over configs: v2 with 5 agents, 2 + 5 * 3 + 4 = 21)
 constexpr int MAXV = 16;
 constexpr int MAXDRAW = 16;
 
-// Compile-time dimensions per env id.  CMAX = fixture pairs on different bodies with at
-// least one dynamic body (upper bound on live contacts).
-template <int ENV> struct Dims;
-template <> struct Dims<0> { static constexpr int V = 0, NA = 2, NB = 1, NF = 8, CMAX = 21, OBS = 28, ACT = 6, NDRAW = 7; };
-template <> struct Dims<1> { static constexpr int V = 0, NA = 5, NB = 1, NF = 11, CMAX = 48, OBS = 40, ACT = 15, NDRAW = 13; };
-template <> struct Dims<2> { static constexpr int V = 2, NA = 2, NB = 1, NF = 12, CMAX = 53, OBS = 39, ACT = 4, NDRAW = 7; };
-template <> struct Dims<3> { static constexpr int V = 2, NA = 2, NB = 1, NF = 12, CMAX = 53, OBS = 39, ACT = 4, NDRAW = 7; };
-template <> struct Dims<4> { static constexpr int V = 2, NA = 2, NB = 3, NF = 15, CMAX = 91, OBS = 69, ACT = 4, NDRAW = 9; };
-template <> struct Dims<5> { static constexpr int V = 3, NA = 2, NB = 1, NF = 8, CMAX = 21, OBS = 27, ACT = 6, NDRAW = 7; };
-template <> struct Dims<6> { static constexpr int V = 3, NA = 2, NB = 1, NF = 8, CMAX = 21, OBS = 27, ACT = 6, NDRAW = 7; };
+// The registry: one row per env id, X(id, version (0 v0, 2 v2, 3 v3), agents, blocks, heavy block,
+// registered TimeLimit), in id order.  N_ENVS, ENV_CFG, Dims<ENV> and the launch table of mrp_ops.h
+// expand from it; build.py compiles one env unit per row, and gym_puzzles_amd/spawn.py restates the
+// rows with their names (tests/test_abi.py compares the two).
+// clang-format off
+#define MRP_ENV_LIST(X) \
+    X(0, 0, 2, 1, 0, 2000) \
+    X(1, 0, 5, 1, 1, 3000) \
+    X(2, 2, 2, 1, 0, 2000) \
+    X(3, 2, 2, 1, 1, 2000) \
+    X(4, 2, 2, 3, 1, 2000) \
+    X(5, 3, 2, 1, 0, 1500) \
+    X(6, 3, 2, 1, 1, 1500) \
+    X(7, 2, 1, 1, 0, 2000) \
+    X(8, 2, 3, 1, 0, 2000) \
+    X(9, 2, 4, 1, 0, 2000) \
+    X(10, 2, 5, 1, 0, 2000) \
+    X(11, 2, 1, 1, 1, 2000) \
+    X(12, 2, 3, 1, 1, 2000) \
+    X(13, 2, 4, 1, 1, 2000) \
+    X(14, 2, 5, 1, 1, 2000) \
+    X(15, 3, 1, 1, 0, 1500) \
+    X(16, 3, 3, 1, 0, 1500) \
+    X(17, 3, 4, 1, 0, 1500) \
+    X(18, 3, 5, 1, 0, 1500) \
+    X(19, 3, 1, 1, 1, 1500) \
+    X(20, 3, 3, 1, 1, 1500) \
+    X(21, 3, 4, 1, 1, 1500) \
+    X(22, 3, 5, 1, 1, 1500)
+// clang-format on
+
+struct EnvCfg { int id, version, n_agents, n_blocks, heavy, max_steps; };
+#define MRP_ENV_CFG_ROW(id, version, n_agents, n_blocks, heavy, max_steps) {id, version, n_agents, n_blocks, heavy, max_steps},
+constexpr EnvCfg ENV_CFG[] = {MRP_ENV_LIST(MRP_ENV_CFG_ROW)};
+#undef MRP_ENV_CFG_ROW
+constexpr int N_ENVS = sizeof(ENV_CFG) / sizeof(ENV_CFG[0]);
+constexpr bool env_rows_in_id_order() {
+    for (int i = 0; i < N_ENVS; ++i)
+        if (ENV_CFG[i].id != i) return false;
+    return true;
+}
+static_assert(env_rows_in_id_order(), "row i of MRP_ENV_LIST is env id i");
+
+// Compile-time dimensions per env id: one family per version, selected by the registry row.
+// CMAX = fixture pairs on different bodies with at least one dynamic body, not both static (upper
+// bound on live contacts).
 // MultiRobotPuzzle2(num_agents = N) (multi_robot_puzzle_02.py:139): one T block (2 fixtures),
-// N agents (body + 2 wheels), 4 walls; CMAX = fixture pairs on different bodies, not both static
+// N agents (body + 2 wheels), 4 walls
 template <int N> struct DimsV2 {
     static constexpr int DF = 2 + 3 * N;   // dynamic fixtures
     static constexpr int V = 2, NA = N, NB = 1, NF = DF + 4, CMAX = DF * (DF - 1) / 2 - 1 - 3 * N + 4 * DF,
                          OBS = 9 * N + 4 + 16 + 1, ACT = 2 * N, NDRAW = 1 + 2 * N + 2;
 };
-template <> struct Dims<7> : DimsV2<1> {};
-template <> struct Dims<8> : DimsV2<3> {};
-template <> struct Dims<9> : DimsV2<4> {};
-template <> struct Dims<10> : DimsV2<5> {};
-template <> struct Dims<11> : DimsV2<1> {};
-template <> struct Dims<12> : DimsV2<3> {};
-template <> struct Dims<13> : DimsV2<4> {};
-template <> struct Dims<14> : DimsV2<5> {};
 // RobotPuzzleBase(num_agents = N) (core.py:88,106,230): one T block (2 fixtures), N Robots (1 fixture), 4 walls
 template <int N> struct DimsV3 {
     static constexpr int DF = 2 + N;
     static constexpr int V = 3, NA = N, NB = 1, NF = DF + 4, CMAX = DF * (DF - 1) / 2 - 1 + 4 * DF,
                          OBS = 4 * N + 3 + 16, ACT = 3 * N, NDRAW = 3 + 2 * N;
 };
-template <> struct Dims<15> : DimsV3<1> {};
-template <> struct Dims<16> : DimsV3<3> {};
-template <> struct Dims<17> : DimsV3<4> {};
-template <> struct Dims<18> : DimsV3<5> {};
-template <> struct Dims<19> : DimsV3<1> {};
-template <> struct Dims<20> : DimsV3<3> {};
-template <> struct Dims<21> : DimsV3<4> {};
-template <> struct Dims<22> : DimsV3<5> {};
-static_assert(DimsV2<2>::CMAX == Dims<2>::CMAX && DimsV2<2>::OBS == Dims<2>::OBS && DimsV2<2>::NF == Dims<2>::NF &&
-              DimsV2<2>::NDRAW == Dims<2>::NDRAW, "DimsV2 restates the registered v2 layout");
-static_assert(DimsV3<2>::CMAX == Dims<5>::CMAX && DimsV3<2>::OBS == Dims<5>::OBS && DimsV3<2>::NF == Dims<5>::NF &&
-              DimsV3<2>::NDRAW == Dims<5>::NDRAW && DimsV3<2>::ACT == Dims<5>::ACT, "DimsV3 restates the v3 layout");
-constexpr int N_ENVS = 23;
-
-// Per env id: version (0 v0, 2 v2, 3 v3), agents, blocks, heavy block, registered TimeLimit.
-struct EnvCfg { int version, n_agents, n_blocks, heavy, max_steps; };
-constexpr EnvCfg ENV_CFG[N_ENVS] = {
-    {0, 2, 1, 0, 2000}, {0, 5, 1, 1, 3000}, {2, 2, 1, 0, 2000}, {2, 2, 1, 1, 2000}, {2, 2, 3, 1, 2000},
-    {3, 2, 1, 0, 1500}, {3, 2, 1, 1, 1500},
-    {2, 1, 1, 0, 2000}, {2, 3, 1, 0, 2000}, {2, 4, 1, 0, 2000}, {2, 5, 1, 0, 2000},
-    {2, 1, 1, 1, 2000}, {2, 3, 1, 1, 2000}, {2, 4, 1, 1, 2000}, {2, 5, 1, 1, 2000},
-    {3, 1, 1, 0, 1500}, {3, 3, 1, 0, 1500}, {3, 4, 1, 0, 1500}, {3, 5, 1, 0, 1500},
-    {3, 1, 1, 1, 1500}, {3, 3, 1, 1, 1500}, {3, 4, 1, 1, 1500}, {3, 5, 1, 1, 1500},
+// v0 has v3's bodies, actions and draws; its observation carries one more word
+template <int N> struct DimsV0 : DimsV3<N> {
+    static constexpr int V = 0, OBS = 4 * N + 20;
 };
+template <int VERSION, int NA, int NB> struct DimsOf;   // a row no family covers does not compile
+template <int N> struct DimsOf<0, N, 1> : DimsV0<N> {};
+template <int N> struct DimsOf<2, N, 1> : DimsV2<N> {};
+template <int N> struct DimsOf<3, N, 1> : DimsV3<N> {};
+// Heavy-v2 with the build-defined 3-block square: its block fixtures are not a formula
+template <> struct DimsOf<2, 2, 3> { static constexpr int V = 2, NA = 2, NB = 3, NF = 15, CMAX = 91, OBS = 69, ACT = 4, NDRAW = 9; };
+template <int ENV> struct Dims : DimsOf<ENV_CFG[ENV].version, ENV_CFG[ENV].n_agents, ENV_CFG[ENV].n_blocks> {};
 
 // Node pool of a lane's dynamic tree.  b2DynamicTree starts at 16 nodes and doubles only when
 // all are live; a world holds at most 2 * proxies - 1 live nodes, so an env with <= 8 proxies

@@ -1,7 +1,7 @@
 // mrp_kernels.hip -- the C ABI (include/mrp.h) of libmrp.so and the env-independent kernels.
 //
-// The lane kernels of each env id live in their own translation unit (mrp_env<E>.hip, built
-// from mrp_lane.h) and are reached through the EnvOps launch table of mrp_ops.h.
+// The lane kernels of each env id live in their own translation unit (mrp_unit.hip with
+// MRP_ENV = E, built from mrp_lane.h) and are reached through the EnvOps launch table of mrp_ops.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -220,10 +220,8 @@ int mrp_create(int env_id, int n_lanes, int device, uint64_t seed, uint64_t lane
         const int resident = cus * 4 * env_ops(env_id)->step_waves_per_eu;
         if ((env_id == 1 || env_id == 5) && n_lanes > resident) ctx->schedule = 1;
     }
-    EnvTables all[N_ENVS];
-    for (int i = 0; i < N_ENVS; ++i) build_tables(i, all[i]);
-    for (int i = 0; i < N_ENVS; ++i)   // every unit keeps its own __constant__ copy
-        if ((e = env_ops(i)->upload_tables(all)) != hipSuccess) return fail("hipMemcpyToSymbol", e);
+    // every unit keeps its own __constant__ copy, and its kernels read no other
+    if ((e = env_ops(env_id)->upload_tables(tables)) != hipSuccess) return fail("hipMemcpyToSymbol", e);
     if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
     ctx->stream = ctx->own_stream;
     size_t nl = (size_t)n_lanes;
@@ -572,11 +570,11 @@ int mrp_debug_progress(int device, uint32_t** host_words, int n_lanes) {
 int mrp_debug_velbench(int device, int nc, int pcount, int iters, int blocks, uint64_t* cycles) {
     const int ncc = nc >= 100 ? nc - 100 : nc;   // nc >= 100: a chain of nc - 100 contacts (k_velbench); ncc + 1 bodies <= v0's 7
     if (ncc < 1 || ncc > 6 || pcount < 1 || pcount > 2 || blocks < 1 || !cycles || hipSetDevice(device) != hipSuccess) return MRP_E_ARG;
-    EnvTables all[N_ENVS];
-    for (int i = 0; i < N_ENVS; ++i) build_tables(i, all[i]);
+    EnvTables v0;
+    build_tables(0, v0);
     unsigned long long* d = nullptr;
     if (hipMalloc((void**)&d, (size_t)blocks * 8) != hipSuccess) return MRP_E_HIP;
-    hipError_t e = velbench_launch(all, nc, pcount, iters, blocks, d);
+    hipError_t e = velbench_launch(v0, nc, pcount, iters, blocks, d);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(cycles, d, (size_t)blocks * 8, hipMemcpyDeviceToHost);
     (void)hipFree(d);
@@ -586,11 +584,11 @@ int mrp_debug_velbench(int device, int nc, int pcount, int iters, int blocks, ui
 int mrp_debug_posbench(int device, int nc, int pcount, int iters, int blocks, uint64_t* out) {
     if (nc < 1 || nc > 6 || pcount < 1 || pcount > 2 || iters < 1 || blocks < 1 || !out || hipSetDevice(device) != hipSuccess)
         return MRP_E_ARG;
-    EnvTables all[N_ENVS];
-    for (int i = 0; i < N_ENVS; ++i) build_tables(i, all[i]);
+    EnvTables v0;
+    build_tables(0, v0);
     unsigned long long* d = nullptr;
     if (hipMalloc((void**)&d, (size_t)blocks * 16) != hipSuccess) return MRP_E_HIP;
-    hipError_t e = posbench_launch(all, nc, pcount, iters, blocks, d);
+    hipError_t e = posbench_launch(v0, nc, pcount, iters, blocks, d);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)blocks * 16, hipMemcpyDeviceToHost);
     (void)hipFree(d);

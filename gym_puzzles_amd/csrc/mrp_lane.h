@@ -1,5 +1,5 @@
 // mrp_lane.h -- the lane kernels of one env id, included once per translation unit by
-// mrp_env<E>.hip with MRP_ENV set (build.py compiles the seven units in parallel).
+// mrp_unit.hip with MRP_ENV set (build.py compiles one unit per env id, in parallel).
 //
 // Execution model: one wavefront (64 threads, one workgroup) owns one world ("lane").  The
 // lane's persistent state is contiguous in HBM (lane-major, so the wave moves it with
@@ -556,8 +556,8 @@ __global__ __launch_bounds__(256) void k_counters(const uint32_t* state, int nl,
 // ------------------------------------------------------------------------------ launch table
 template <int ENV>
 struct Launch {
-    static hipError_t upload_tables(const EnvTables* all) {
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_table), all + ENV, sizeof(EnvTables));
+    static hipError_t upload_tables(const EnvTables& t) {
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_table), &t, sizeof(EnvTables));
     }
     static void init(hipStream_t s, uint32_t* state, int nl) {
         hipLaunchKernelGGL(k_init<ENV>, dim3(nl), dim3(BLOCK), 0, s, state, nl);
@@ -636,7 +636,7 @@ struct Launch {
 #define MRP_DEFINE_ENV_OPS(E) namespace { template struct Launch<E>; }
 #else
 #define MRP_DEFINE_ENV_OPS(E) \
-    namespace mrp { extern const EnvOps g_env_ops_##E; const EnvOps g_env_ops_##E = Launch<E>::ops(); }
+    namespace mrp { const EnvOps MRP_ENV_OPS_NAME(E) = Launch<E>::ops(); }
 #endif
 
 #if MRP_ENV == 0
@@ -718,14 +718,14 @@ __global__ __launch_bounds__(BLOCK, MRP_STEP_WAVES_PER_EU) void k_posbench(int n
     if (tid == 0) { out[2 * blockIdx.x] = t1 - t0 + (is.pcx[0] == 12345.0f ? 1ull : 0ull); out[2 * blockIdx.x + 1] = (unsigned long long)n; }
 }
 }  // namespace
-hipError_t mrp::posbench_launch(const EnvTables* all, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), all, sizeof(EnvTables));
+hipError_t mrp::posbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), &v0, sizeof(EnvTables));
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_posbench, dim3(blocks), dim3(BLOCK), 0, nullptr, nc, pcount, iters, d_out);
     return hipGetLastError();
 }
-hipError_t mrp::velbench_launch(const EnvTables* all, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), all, sizeof(EnvTables));
+hipError_t mrp::velbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), &v0, sizeof(EnvTables));
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_velbench, dim3(blocks), dim3(BLOCK), 0, nullptr, nc, pcount, iters, d_out);
     return hipGetLastError();

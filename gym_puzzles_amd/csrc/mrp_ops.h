@@ -1,8 +1,8 @@
 // mrp_ops.h -- the per-env launch table between the C ABI (mrp_kernels.hip) and the per-env
-// kernel translation units (mrp_env0.hip .. mrp_env6.hip).
+// kernel translation units (mrp_unit.hip, compiled once per env id with -DMRP_ENV=<id>).
 //
 // Every env id is its own template instantiation of the whole lane step (k_step<ENV> and
-// friends), and each instantiation is compiled in its own translation unit so the seven
+// friends), and each instantiation is compiled in its own translation unit so the N_ENVS
 // builds run in parallel (build.py).  A translation unit exports one EnvOps: plain host
 // functions that launch its kernels on a given stream.  The C ABI never names a kernel.
 #pragma once
@@ -25,8 +25,6 @@ constexpr int RPPT = 8;        // pixels per thread: one display-list build serv
 }  // namespace mrpr
 
 namespace mrp {
-
-constexpr int BLOCK = 64;      // one wave per workgroup: lanes of a block never wait on each other
 
 // k_step's arguments (mrp_step_device_ex)
 struct StepArgs {
@@ -63,7 +61,7 @@ struct EnvOps {
     // word offset of cnext (the first of `cslot_arrays` contiguous arrays of `cslot_n` words) and of cHW
     int cslot_word, cslot_n, cslot_arrays, chw_word;
     int step_waves_per_eu;     // k_step's launch bound: resident waves per SIMD (mrp_create: resident lanes)
-    hipError_t (*upload_tables)(const EnvTables* all);   // all N_ENVS tables -> this unit's __constant__ copy
+    hipError_t (*upload_tables)(const EnvTables& t);   // this env's tables -> its unit's __constant__ copy
     void (*init)(hipStream_t, uint32_t* state, int nl);
     void (*reset)(hipStream_t, uint32_t* state, int nl, const uint8_t* mask, const double* draws, const float* actions,
                   float* obs, const EnvParams& P, uint64_t seed, uint64_t lane_offset);
@@ -80,21 +78,20 @@ struct EnvOps {
     hipError_t (*debug_progress)(uint32_t* dev_words);
 };
 
-// defined in mrp_env<E>.hip
-extern const EnvOps g_env_ops_0, g_env_ops_1, g_env_ops_2, g_env_ops_3, g_env_ops_4, g_env_ops_5, g_env_ops_6,
-    g_env_ops_7, g_env_ops_8, g_env_ops_9, g_env_ops_10, g_env_ops_11, g_env_ops_12, g_env_ops_13, g_env_ops_14,
-    g_env_ops_15, g_env_ops_16, g_env_ops_17, g_env_ops_18, g_env_ops_19, g_env_ops_20, g_env_ops_21, g_env_ops_22;
-// defined in mrp_env0.hip: the lane-distributed velocity-sweep micro-benchmark (mrp_debug_velbench)
-hipError_t velbench_launch(const EnvTables* all, int nc, int pcount, int iters, int blocks, unsigned long long* d_out);
-// defined in mrp_env0.hip: the position-pass micro-benchmark (mrp_debug_posbench)
-hipError_t posbench_launch(const EnvTables* all, int nc, int pcount, int iters, int blocks, unsigned long long* d_out);
+// one EnvOps per row of the registry (mrp_config.h), defined by the unit compiled with MRP_ENV = id
+#define MRP_ENV_OPS_NAME(id) g_env_ops_##id
+#define MRP_ENV_OPS_DECL(id, ...) extern const EnvOps MRP_ENV_OPS_NAME(id);
+MRP_ENV_LIST(MRP_ENV_OPS_DECL)
+#undef MRP_ENV_OPS_DECL
+// defined in env 0's unit: the lane-distributed velocity-sweep micro-benchmark (mrp_debug_velbench)
+// and the position-pass micro-benchmark (mrp_debug_posbench), on v0's tables
+hipError_t velbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out);
+hipError_t posbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out);
 
 inline const EnvOps* env_ops(int env_id) {
-    static const EnvOps* const t[N_ENVS] = {&g_env_ops_0,  &g_env_ops_1,  &g_env_ops_2,  &g_env_ops_3,  &g_env_ops_4,
-                                            &g_env_ops_5,  &g_env_ops_6,  &g_env_ops_7,  &g_env_ops_8,  &g_env_ops_9,
-                                            &g_env_ops_10, &g_env_ops_11, &g_env_ops_12, &g_env_ops_13, &g_env_ops_14,
-                                            &g_env_ops_15, &g_env_ops_16, &g_env_ops_17, &g_env_ops_18, &g_env_ops_19,
-                                            &g_env_ops_20, &g_env_ops_21, &g_env_ops_22};
+#define MRP_ENV_OPS_ENTRY(id, ...) &MRP_ENV_OPS_NAME(id),
+    static const EnvOps* const t[N_ENVS] = {MRP_ENV_LIST(MRP_ENV_OPS_ENTRY)};
+#undef MRP_ENV_OPS_ENTRY
     return env_id >= 0 && env_id < N_ENVS ? t[env_id] : nullptr;
 }
 

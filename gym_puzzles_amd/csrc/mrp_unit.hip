@@ -1,0 +1,5 @@
+// mrp_unit.hip -- one env id's lane kernels and launch table (see mrp_lane.h, mrp_ops.h).
+// build.py compiles this file once per row of the registry (mrp_config.h) with -DMRP_ENV=<id>.
+#include "mrp_lane.h"
+
+MRP_DEFINE_ENV_OPS(MRP_ENV)

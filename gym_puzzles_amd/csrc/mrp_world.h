@@ -549,6 +549,7 @@ template <int ENV> struct World {
     // last created, fixtures newest first), which is the order the tree's shape depends on.
     __device__ __forceinline__ void sync_fixtures_coop(uint32_t bflag) {
         static_assert(NF <= 64, "one lane per fixture");
+        static_assert(BLOCK == 64, "a workgroup is one wave: that alone orders the wave's reads after thread 0's writes");
         const unsigned long long tf = MRP_NOW();
         const int f = tid < NF ? tid : 0;
         const int b = L.fix_body[f];
@@ -2048,6 +2049,7 @@ template <int ENV> struct World {
     // depth and the counts are wave-uniform.
     static constexpr int NLW = (C + 63) / 64;   // list words per lane
     __device__ __forceinline__ void solve_coop(float h, float dtRatio) {
+        static_assert(BLOCK == 64, "a workgroup is one wave: that alone orders the wave's reads after thread 0's writes");
         Isl& is = sh.isl;
         uint32_t bflag = 0;   // body island flags (bit per body), wave-uniform
         int seed = ND - 1;    // next DFS seed

@@ -24,14 +24,38 @@ _V2_SCALE, _V2_W, _V2_H, _V2_BORDER, _V2_GOAL_BORDER = 140.0 * 4, 1440, 810, 0.3
 # v3 constants (core.py:16-19, 97-98)
 _V3_SCALE, _V3_W, _V3_H, _V3_BORDER = 30.0, 640, 480, 1
 
-# env id -> (version, agents, blocks, heavy) (csrc/mrp_config.h ENV_CFG); ids 7-10 / 11-14 are
-# MultiRobotPuzzle2 / MultiRobotPuzzleHeavy2 constructed with num_agents = 1, 3, 4, 5, ids 15-18 /
-# 19-22 RobotPuzzleBase(num_agents = 1, 3, 4, 5) with heavy False / True
-ENV_CFG = {0: (0, 2, 1, 0), 1: (0, 5, 1, 1), 2: (2, 2, 1, 0), 3: (2, 2, 1, 1), 4: (2, 2, 3, 1), 5: (3, 2, 1, 0), 6: (3, 2, 1, 1),
-           7: (2, 1, 1, 0), 8: (2, 3, 1, 0), 9: (2, 4, 1, 0), 10: (2, 5, 1, 0),
-           11: (2, 1, 1, 1), 12: (2, 3, 1, 1), 13: (2, 4, 1, 1), 14: (2, 5, 1, 1),
-           15: (3, 1, 1, 0), 16: (3, 3, 1, 0), 17: (3, 4, 1, 0), 18: (3, 5, 1, 0),
-           19: (3, 1, 1, 1), 20: (3, 3, 1, 1), 21: (3, 4, 1, 1), 22: (3, 5, 1, 1)}
+# The env registry, row e = env id e: (name, version, agents, blocks, heavy).  It restates the rows of
+# csrc/mrp_config.h's MRP_ENV_LIST with their names (tests/test_abi.py compares the two); every table
+# below derives from it.
+_ENVS = (
+    ("MultiRobotPuzzle-v0", 0, 2, 1, 0),
+    ("MultiRobotPuzzleHeavy-v0", 0, 5, 1, 1),
+    ("MultiRobotPuzzle-v2", 2, 2, 1, 0),
+    ("MultiRobotPuzzleHeavy-v2", 2, 2, 1, 1),
+    ("MultiRobotPuzzleHeavy-v2-3block", 2, 2, 3, 1),
+    ("MultiRobotPuzzle-v3", 3, 2, 1, 0),
+    ("MultiRobotPuzzle-v3-heavy", 3, 2, 1, 1),      # RobotPuzzleBase(heavy=True) (tests/test_env.py:12)
+    # MultiRobotPuzzle2 / MultiRobotPuzzleHeavy2(num_agents=N) (multi_robot_puzzle_02.py:139)
+    ("MultiRobotPuzzle-v2-agents1", 2, 1, 1, 0),
+    ("MultiRobotPuzzle-v2-agents3", 2, 3, 1, 0),
+    ("MultiRobotPuzzle-v2-agents4", 2, 4, 1, 0),
+    ("MultiRobotPuzzle-v2-agents5", 2, 5, 1, 0),
+    ("MultiRobotPuzzleHeavy-v2-agents1", 2, 1, 1, 1),
+    ("MultiRobotPuzzleHeavy-v2-agents3", 2, 3, 1, 1),
+    ("MultiRobotPuzzleHeavy-v2-agents4", 2, 4, 1, 1),
+    ("MultiRobotPuzzleHeavy-v2-agents5", 2, 5, 1, 1),
+    # RobotPuzzleBase(num_agents=N[, heavy=True]) (core.py:86-106)
+    ("MultiRobotPuzzle-v3-agents1", 3, 1, 1, 0),
+    ("MultiRobotPuzzle-v3-agents3", 3, 3, 1, 0),
+    ("MultiRobotPuzzle-v3-agents4", 3, 4, 1, 0),
+    ("MultiRobotPuzzle-v3-agents5", 3, 5, 1, 0),
+    ("MultiRobotPuzzle-v3-heavy-agents1", 3, 1, 1, 1),
+    ("MultiRobotPuzzle-v3-heavy-agents3", 3, 3, 1, 1),
+    ("MultiRobotPuzzle-v3-heavy-agents4", 3, 4, 1, 1),
+    ("MultiRobotPuzzle-v3-heavy-agents5", 3, 5, 1, 1),
+)
+ENV_IDS = {row[0]: e for e, row in enumerate(_ENVS)}       # name -> env id
+ENV_CFG = {e: row[1:] for e, row in enumerate(_ENVS)}      # env id -> (version, agents, blocks, heavy)
 ENV_VERSION = {e: c[0] for e, c in ENV_CFG.items()}
 N_AGENTS = {e: c[1] for e, c in ENV_CFG.items()}
 N_BLOCKS = {e: c[2] for e, c in ENV_CFG.items()}

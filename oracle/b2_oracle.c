@@ -1338,8 +1338,8 @@ static int period_scan(const float* hist, int ns, int iters) {
     return first;
 }
 
-/* The device's early-exit compare schedule (mrp_world.h exit_mask, MRP_EXIT_DENSE = 32 /
- * MRP_EXIT_SPARSE = 16): after sweep `done` the state is compared with the snapshot of two sweeps
+/* The device's early-exit compare schedule (mrp_world.h exit_mask, EXIT_DENSE = 32 /
+ * EXIT_SPARSE = 16): after sweep `done` the state is compared with the snapshot of two sweeps
  * earlier when (iters - done) & mask == 0 and snapshotted when it is 2.  One definition for the work
  * model (the device sweep counts of tools/roofline_model.py) and the early-exit CPU port. */
 #define OR_EXIT_DENSE 32

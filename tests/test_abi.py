@@ -14,6 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mrp.h")
+CONFIG = os.path.join(ROOT, "gym_puzzles_amd", "csrc", "mrp_config.h")
 
 
 def _declared():
@@ -124,3 +125,26 @@ def test_status_flag_bits_agree():
     assert f"#define MRP_STATUS_NONFINITE 0x{_native.STATUS_NONFINITE:x}" in src
     assert f"#define MRP_STATUS_FAULT 0x{_native.STATUS_FAULT:x}" in src
     assert f"#define MRP_STATUS_KIND_MASK 0x{_native.STATUS_KIND_MASK:x}" in src
+
+
+def test_env_registry_agrees_with_python():
+    """The rows of csrc/mrp_config.h's MRP_ENV_LIST (the only list of env ids on the C++ side) equal
+    spawn.py's table for every id, and the names cover exactly the ids 0..N_ENVS-1."""
+    from gym_puzzles_amd import ENV_IDS, spawn
+    rows = [tuple(int(v) for v in r.split(",")) for r in re.findall(r"^\s*X\(([\d,\s]+)\)", open(CONFIG).read(), re.M)]
+    n_envs = len(rows)
+    assert n_envs > 0 and [r[0] for r in rows] == list(range(n_envs)), "row i is env id i"
+    assert len(ENV_IDS) == n_envs and sorted(ENV_IDS.values()) == list(range(n_envs))
+    assert sorted(spawn.ENV_CFG) == list(range(n_envs))
+    for env_id, version, agents, blocks, heavy, _max_steps in rows:
+        assert spawn.ENV_CFG[env_id] == (version, agents, blocks, heavy), env_id
+
+
+def test_build_units_follow_the_registry():
+    """build.py compiles one object per env id plus the three shared units, and flags only known ids."""
+    from gym_puzzles_amd import ENV_IDS, build as b
+    assert b.N_ENVS == len(ENV_IDS)
+    assert all(type(k) is int and 0 <= k < b.N_ENVS for k in b.UNIT_FLAGS), sorted(b.UNIT_FLAGS, key=str)
+    assert sorted(e for _, _, e in b.SOURCES if e is not None) == list(range(b.N_ENVS))
+    assert sorted(s for s, _, e in b.SOURCES if e is None) == ["mrp_kernels.hip", "mrp_norm.hip", "mrp_tables.cpp"]
+    assert len({o for _, o, _ in b.SOURCES}) == len(b.SOURCES) == b.N_ENVS + 3, "one object per unit"

@@ -330,6 +330,34 @@ def test_costliest_first_schedule_changes_nothing(gpu_lib, env_id, lanes, explic
     b.close()
 
 
+def test_two_units_alive_at_once_keep_their_own_tables(gpu_lib):
+    """mrp_create uploads a context's tables into its own env unit only.  Envs 15 and 19 (one agent, light /
+    heavy block) share their Dims but not their tables: two contexts alive at once and stepped alternately
+    give, bit for bit, what a context of the same id gives stepped alone in a fresh Batch.  A table that
+    reached the wrong unit would otherwise show only as a physics mismatch far from its cause."""
+    from gym_puzzles_amd import Batch
+    lanes, steps, seed = 2, 8, 31
+
+    def run(env_ids):
+        bs = [Batch(e, lanes, seed=seed) for e in env_ids]
+        rows = [[("reset", b.reset().copy())] for b in bs]
+        for t in range(steps):
+            for b, r in zip(bs, rows):   # alternately: one step of each context per round
+                b.step()                 # device-RNG actions
+                r += [(f"obs@{t}", b.obs.copy()), (f"reward64@{t}", b.reward64.copy()), (f"done@{t}", b.done.copy()),
+                      (f"status@{t}", b.status.copy())]
+        for b in bs:
+            b.close()
+        return rows
+
+    together = run((15, 19))
+    assert not np.array_equal(together[0][0][1], together[1][0][1]), "the two envs' tables give different worlds"
+    for env_id, both in zip((15, 19), together):
+        alone, = run((env_id,))
+        for (name, g), (_, c) in zip(both, alone):
+            _eq(f"env {env_id} {name}", g, c)
+
+
 @pytest.mark.parametrize("env_id", list(ENVS) + list(AGENT_VARIANTS))
 def test_whole_episode_soak(gpu_lib, orc, env_id):
     """One whole episode at the registered TimeLimit (2000 / 3000 / 1500 steps) plus 50 steps of

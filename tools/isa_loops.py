@@ -1,6 +1,6 @@
 """Instruction mix of the loops of one kernel in a gfx950 assembly listing (CPU only).
 
-    hipcc <build.py FLAGS> --cuda-device-only -S gym_puzzles_amd/csrc/mrp_env<E>.hip -o env<E>.s
+    hipcc <build.py FLAGS> --cuda-device-only -S -DMRP_ENV=<E> gym_puzzles_amd/csrc/mrp_unit.hip -o env<E>.s
     python tools/isa_loops.py env<E>.s 'k_stepILi<E>ELb0E' [--all]
 
 LLVM annotates every basic block of a loop with its header (`; =>This Inner Loop Header: Depth=d`,

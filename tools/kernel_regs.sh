@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register use / spills of every k_step instantiation in a built env unit object (CPU only):
-#   tools/kernel_regs.sh gym_puzzles_amd/build/libmrp.so.obj/mrp_env0.hip.o
+#   tools/kernel_regs.sh gym_puzzles_amd/build/libmrp.so.obj/mrp_env0.o
 set -euo pipefail
 O=$1
 T=$(mktemp -d)

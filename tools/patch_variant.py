@@ -5,7 +5,7 @@ untouched, so experiment arms never enter the shipped headers):
     MRP_VARIANT_WORKTREE=1 python tools/patch_variant.py ...           (base: the working tree)
 
 SPEC.py defines EDITS = [(file, old, new), ...] (exact text replacements, each `old` must occur
-in the file), optionally FLAGS = {"mrp_envE.hip": [...]} (that unit's compile flags instead of
+in the file), optionally FLAGS = {E: [...]} (env id E's compile flags instead of
 build.py's UNIT_FLAGS entry) and DEFINES = ["NAME", ...] (-D for every unit, e.g. MRP_STAMPS).  Only the listed env units are compiled from the patched copy; the other
 units are the default library's objects (python -m gym_puzzles_amd.build first).  Every edit must keep
 the LaneState / EnvOps layout (mrp_create checks each unit's compiled dims).
@@ -47,12 +47,13 @@ def main():
         if n == 0:
             raise SystemExit(f"{spec}: edit not found in {f}: {old[:80]!r}")
         open(p, "w").write(txt.replace(old, new))
-    B.CSRC = csrc
-    B.SOURCES = [os.path.join(csrc, os.path.basename(x)) for x in B.SOURCES]
-    B.DEPS = B.SOURCES + [os.path.join(csrc, os.path.basename(x)) for x in B.DEPS if x.endswith(".h")]
-    B.UNIT_FLAGS = dict(B.UNIT_FLAGS, **s.get("FLAGS", {}))
+    flags = s.get("FLAGS", {})
+    unknown = sorted(set(flags) - set(range(B.N_ENVS)), key=str)
+    if unknown:
+        raise SystemExit(f"{spec}: FLAGS keys are env ids (0..{B.N_ENVS - 1}), not {unknown}")
+    B.UNIT_FLAGS = {**B.UNIT_FLAGS, **flags}
     os.environ["MRP_ALLOW_STALE_UNITS"] = "1"
-    print(B.build(verbose=True, out=out, only_envs=envs, defines=tuple(s.get("DEFINES", ()))))
+    print(B.build(verbose=True, out=out, only_envs=envs, defines=tuple(s.get("DEFINES", ())), csrc=csrc))
 
 
 if __name__ == "__main__":

@@ -10,4 +10,4 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from gym_puzzles_amd.build import UNIT_FLAGS  # noqa: E402
 
-FLAGS = {"mrp_env5.hip": list(UNIT_FLAGS["mrp_env5.hip"]) + ["-DMRP_VEL_BFREE=1", "-DMRP_VEL_BFREE_REGS=1"]}
+FLAGS = {5: list(UNIT_FLAGS[5]) + ["-DMRP_VEL_BFREE=1", "-DMRP_VEL_BFREE_REGS=1"]}

@@ -7,4 +7,4 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from gym_puzzles_amd.build import UNIT_FLAGS  # noqa: E402
 
 EDITS = []
-FLAGS = {u: list(UNIT_FLAGS.get(u, [])) + ["-DMRP_FRESH_REGS=1"] for u in ("mrp_env1.hip", "mrp_env2.hip", "mrp_env4.hip")}
+FLAGS = {u: list(UNIT_FLAGS.get(u, [])) + ["-DMRP_FRESH_REGS=1"] for u in (1, 2, 4)}

@@ -9,4 +9,4 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from gym_puzzles_amd.build import UNIT_FLAGS  # noqa: E402
 
 EDITS = []
-FLAGS = {u: list(UNIT_FLAGS[u]) + ["-DMRP_STEP_WAVES_PER_EU=4"] for u in ("mrp_env0.hip", "mrp_env5.hip")}
+FLAGS = {u: list(UNIT_FLAGS[u]) + ["-DMRP_STEP_WAVES_PER_EU=4"] for u in (0, 5)}
