@@ -17,7 +17,7 @@
  * Compile with -O2 -ffp-contract=off -fno-fast-math (IEEE float32, no FMA contraction),
  * matching how the box2d-py wheel's C++ is built for baseline x86-64.
  */
-#include "b2_oracle.h"
+#include "b2_work.h"
 
 #include <float.h>
 #include <math.h>
@@ -880,24 +880,6 @@ V2 b2o_world_vector(const Body* b, V2 local) { return mul_rv(b->xf.q, local); }
 float b2o_inertia(const Body* b) { return b->I + b->mass * vdot(b->sweep.localCenter, b->sweep.localCenter); }
 
 /* ---------------------------------------------------------------- contact solver [B2 b2ContactSolver.cpp] */
-typedef struct { V2 c; float a; } Position;
-typedef struct { V2 v; float w; } Velocity;
-typedef struct { V2 rA, rB; float normalImpulse, tangentImpulse, normalMass, tangentMass, velocityBias; } VCPoint;
-typedef struct {
-    VCPoint points[2]; V2 normal; float nm[4]; /* normalMass ex.x ex.y ey.x ey.y */ float K[4];
-    int indexA, indexB; float invMassA, invMassB, invIA, invIB, friction, restitution, tangentSpeed;
-    int pointCount, contactIndex;
-} VC;
-typedef struct {
-    V2 localPoints[2]; V2 localNormal, localPoint; int indexA, indexB; float invMassA, invMassB;
-    V2 localCenterA, localCenterB; float invIA, invIB; int type; float radiusA, radiusB; int pointCount;
-} PC;
-typedef struct {
-    float dt, inv_dt, dtRatio; int velocityIterations, positionIterations, warmStarting;
-} TimeStep;
-typedef struct {
-    TimeStep step; Position* positions; Velocity* velocities; Contact** contacts; int count; VC* vcs; PC* pcs;
-} Solver;
 
 static void solver_init(Solver* s, TimeStep step, Contact** contacts, int count, Position* pos, Velocity* vel) {
     s->step = step; s->contacts = contacts; s->count = count; s->positions = pos; s->velocities = vel;
@@ -1050,18 +1032,6 @@ static inline V2 mat_mul(const float* M, V2 v) {   /* M = {ex.x, ex.y, ey.x, ey.
     return v2(M[0] * v.x + M[2] * v.y, M[1] * v.x + M[3] * v.y);
 }
 
-/* diagnostic (b2o_lcp_cases): how often each case of the 2-point block solver applies (cases 1-4,
- * then "no solution"), counted over every 2-point velocity update since the last reset; plus the
- * 1-point updates and the updates whose normal impulses are subnormal (tools: chain analysis) */
-#ifndef OR_NO_WORK
-static long g_lcp[8];
-#define LCP_CASE(k) do { _Pragma("omp atomic") g_lcp[k]++; } while (0)
-void b2o_lcp_cases(long* out8, int reset) {
-    for (int k = 0; k < 8; ++k) { if (out8) out8[k] = g_lcp[k]; if (reset) g_lcp[k] = 0; }
-}
-#else
-#define LCP_CASE(k) do {} while (0)
-#endif
 static void solver_solve_velocity(Solver* s) {
     for (int i = 0; i < s->count; ++i) {
         VC* vc = s->vcs + i;
@@ -1110,16 +1080,16 @@ static void solver_solve_velocity(Solver* s) {
             b = vsub(b, mat_mul(vc->K, a));
             for (;;) {
                 V2 x = vneg(mat_mul(vc->nm, b));
-                if (x.x >= 0.0f && x.y >= 0.0f) { LCP_CASE(0); goto apply; }
+                if (x.x >= 0.0f && x.y >= 0.0f) { b2w_lcp_case(0); goto apply; }
                 x.x = -cp1->normalMass * b.x; x.y = 0.0f;
                 vn1 = 0.0f; vn2 = vc->K[1] * x.x + b.y;
-                if (x.x >= 0.0f && vn2 >= 0.0f) { LCP_CASE(1); goto apply; }
+                if (x.x >= 0.0f && vn2 >= 0.0f) { b2w_lcp_case(1); goto apply; }
                 x.x = 0.0f; x.y = -cp2->normalMass * b.y;
                 vn1 = vc->K[2] * x.y + b.x; vn2 = 0.0f;
-                if (x.y >= 0.0f && vn1 >= 0.0f) { LCP_CASE(2); goto apply; }
+                if (x.y >= 0.0f && vn1 >= 0.0f) { b2w_lcp_case(2); goto apply; }
                 x.x = 0.0f; x.y = 0.0f; vn1 = b.x; vn2 = b.y;
-                if (vn1 >= 0.0f && vn2 >= 0.0f) { LCP_CASE(3); goto apply; }
-                LCP_CASE(4);
+                if (vn1 >= 0.0f && vn2 >= 0.0f) { b2w_lcp_case(3); goto apply; }
+                b2w_lcp_case(4);
                 break;
             apply: {
                     V2 d = vsub(x, a);
@@ -1210,10 +1180,6 @@ static int solver_solve_position(Solver* s, int toi, int toiIndexA, int toiIndex
 }
 
 /* ---------------------------------------------------------------- island [B2 b2Island.cpp] */
-typedef struct {
-    Body** bodies; Contact** contacts; Position* positions; Velocity* velocities;
-    int bodyCount, contactCount, bodyCapacity, contactCapacity;
-} Island;
 
 static void island_init(Island* is, int bodyCap, int contactCap) {
     is->bodyCapacity = bodyCap; is->contactCapacity = contactCap;
@@ -1253,409 +1219,56 @@ static void integrate_positions(Island* is, float h, int syncBodies) {
     }
 }
 
-/* ---- work model (OrWork, test infrastructure): device sweep counts and dependency levels ---- */
-/* dependency levels of the island's Gauss-Seidel order: contact i waits for the last earlier
- * contact that shares one of its dynamic bodies (`dyn[k]`: island body k moves under this solve);
- * returns the level count, and the sum over levels of each level's largest point count */
-static int work_levels(const Solver* s, const int* dyn, int* level_points) {
-    int last[256], lvmax_pts[256];
-    int nb = 0;
-    for (int i = 0; i < s->count; ++i) {
-        const int a = s->vcs[i].indexA, b = s->vcs[i].indexB;
-        if (a + 1 > nb) nb = a + 1;
-        if (b + 1 > nb) nb = b + 1;
-    }
-    for (int k = 0; k < nb && k < 256; ++k) last[k] = 0;
-    int L = 0;
-    for (int i = 0; i < s->count && i < 256; ++i) {
-        const int a = s->vcs[i].indexA, b = s->vcs[i].indexB;
-        int lv = 1;
-        if (dyn[a] && last[a] + 1 > lv) lv = last[a] + 1;
-        if (dyn[b] && last[b] + 1 > lv) lv = last[b] + 1;
-        if (dyn[a]) last[a] = lv;
-        if (dyn[b]) last[b] = lv;
-        if (lv > L) { for (int k = L; k < lv; ++k) lvmax_pts[k] = 0; L = lv; }
-        if (s->pcs[i].pointCount > lvmax_pts[lv - 1]) lvmax_pts[lv - 1] = s->pcs[i].pointCount;
-    }
-    int lp = 0;
-    for (int k = 0; k < L; ++k) lp += lvmax_pts[k];
-    if (level_points) *level_points = lp;
-    return L;
-}
-/* critical path of `reps` repetitions of the island's Gauss-Seidel order, each contact lasting
- * its point count (by_points) or 1: a contact starts when the previous contacts that share one of
- * its dynamic bodies have finished (the sweeps unrolled, so sweep k+1 may overlap sweep k) */
-static long work_pipe(const Solver* s, const int* dyn, int reps, int by_points) {
-    long fin[256];
-    int nb = 0;
-    for (int i = 0; i < s->count; ++i) {
-        if (s->vcs[i].indexA + 1 > nb) nb = s->vcs[i].indexA + 1;
-        if (s->vcs[i].indexB + 1 > nb) nb = s->vcs[i].indexB + 1;
-    }
-    for (int k = 0; k < nb && k < 256; ++k) fin[k] = 0;
-    long end = 0;
-    for (int r = 0; r < reps; ++r)
-        for (int i = 0; i < s->count; ++i) {
-            const int a = s->vcs[i].indexA, b = s->vcs[i].indexB;
-            long t = 0;
-            if (dyn[a] && fin[a] > t) t = fin[a];
-            if (dyn[b] && fin[b] > t) t = fin[b];
-            t += by_points ? s->pcs[i].pointCount : 1;
-            if (dyn[a]) fin[a] = t;
-            if (dyn[b]) fin[b] = t;
-            if (t > end) end = t;
-        }
-    return end;
-}
-/* the velocity sweeps with the device's exact early-exit count: the sweep loop always runs all
- * `iters` (results are the reference's), the return value is the number the device runs */
-/* diagnostic (b2o_period_diag): for islands whose sweeps never reach period 1 or 2, the earliest
- * sweep at which the state repeats with ANY period up to 64, histogrammed; [0] islands examined,
- * [1] of them with no repeat within `iters`, [2 + k] first repeat at sweep k (k < 190), and the
- * period histogram at [200 + p] */
-static int g_period_diag = 0;
-static long g_period_hist[300];
-void b2o_period_diag(int on, long* out300) {
-    if (out300) for (int i = 0; i < 300; ++i) out300[i] = g_period_hist[i];
-    if (on >= 0) { g_period_diag = on; for (int i = 0; i < 300; ++i) g_period_hist[i] = 0; }
-}
-static int g_model_period = 0;   /* > 0: the work model counts sweeps as if periods up to this were detected */
-void b2o_model_period(int p) { g_model_period = p; }
-static int period_scan(const float* hist, int ns, int iters) {
-    int first = -1, per = 0;
-    const int pmax = g_model_period > 0 ? g_model_period : 64;
-    for (int k = 1; k <= iters && first < 0; ++k)
-        for (int p = 1; p <= pmax && p <= k; ++p)
-            if (memcmp(hist + (size_t)k * ns, hist + (size_t)(k - p) * ns, sizeof(float) * (size_t)ns) == 0) {
-                first = k; per = p; break;
-            }
-#pragma omp critical
-    {
-        g_period_hist[0]++;
-        if (first < 0) g_period_hist[1]++;
-        else { g_period_hist[2 + (first < 190 ? first : 189)]++; g_period_hist[200 + per]++; }
-    }
-    return first;
-}
-
-/* The device's early-exit compare schedule (mrp_world.h exit_mask, EXIT_DENSE = 32 /
- * EXIT_SPARSE = 16): after sweep `done` the state is compared with the snapshot of two sweeps
- * earlier when (iters - done) & mask == 0 and snapshotted when it is 2.  One definition for the work
- * model (the device sweep counts of tools/roofline_model.py) and the early-exit CPU port. */
-#define OR_EXIT_DENSE 32
-#define OR_EXIT_SPARSE 16
-static inline int exit_mask(int done) { return done > OR_EXIT_DENSE ? OR_EXIT_SPARSE - 1 : 3; }
-
-static int work_velocity_sweeps(Solver* s, int iters, int nbodies) {
-    const int nc = s->count, ns = 4 * nc + 3 * nbodies;
-    float* snap = (float*)malloc(sizeof(float) * (size_t)(ns > 0 ? ns : 1));
-    float* cur = (float*)malloc(sizeof(float) * (size_t)(ns > 0 ? ns : 1));
-#define WORK_STATE(dst) do {                                                                       \
-        int k_ = 0;                                                                                \
-        for (int i_ = 0; i_ < nc; ++i_)                                                            \
-            for (int j_ = 0; j_ < 2; ++j_) {                                                       \
-                (dst)[k_++] = s->vcs[i_].points[j_].normalImpulse;                                 \
-                (dst)[k_++] = s->vcs[i_].points[j_].tangentImpulse;                                \
-            }                                                                                      \
-        for (int b_ = 0; b_ < nbodies; ++b_) {                                                     \
-            (dst)[k_++] = s->velocities[b_].v.x; (dst)[k_++] = s->velocities[b_].v.y;              \
-            (dst)[k_++] = s->velocities[b_].w;                                                     \
-        }                                                                                          \
-    } while (0)
-    int have = (iters & 3) == 2, run = -1;
-    if (have) WORK_STATE(snap);
-    float* hist = (g_period_diag || g_model_period > 0) ? (float*)malloc(sizeof(float) * (size_t)(ns > 0 ? ns : 1) * (size_t)(iters + 1)) : NULL;
-    if (hist) WORK_STATE(hist);
-    for (int it = 0; it < iters; ++it) {
-        solver_solve_velocity(s);
-        if (hist) WORK_STATE(hist + (size_t)(it + 1) * ns);
-        if (run >= 0) continue;
-        const int left = iters - (it + 1), m = exit_mask(it + 1);
-        if ((left & m) == 0 && have) {
-            WORK_STATE(cur);
-            if (memcmp(cur, snap, sizeof(float) * (size_t)ns) == 0) run = it + 1;
-        }
-        if ((left & m) == 2) { WORK_STATE(snap); have = 1; }
-    }
-#undef WORK_STATE
-    if (hist) {
-        if (run < 0 && nc > 0) {
-            const int first = period_scan(hist, ns, iters);
-            if (g_model_period > 0 && first > 0) run = first;
-        }
-        free(hist);
-    }
-    free(snap);
-    free(cur);
-    return run >= 0 ? run : iters;
-}
-
-/* diagnostic (b2o_model_2wave): the island's `sweeps` velocity sweeps (device
- * count, `iters` configured) priced on one wave, and split over two waves of one workgroup.  Each
- * wave runs its contacts in the island's Gauss-Seidel order; a contact starts when its wave is free
- * and every dynamic body it touches holds the value of the body's previous update in sequential order
- * (+x cycles when that update ran on the other wave: an LDS handoff), so the split is bit-exact by
- * construction.  At each early-exit compare point the waves meet (+b).  The partition (contact 0 on
- * wave 0) is the best of all 2^(nc-1) for nc <= 12 over the first min(sweeps, 8) sweeps. */
-static double g2w_cost[16], g2w_x = -1.0, g2w_b = 0.0, g2w_read = 0.0, g2w_pub = 0.0;
-void b2o_model_2wave(const double* cost16, double x, double b) {
-    if (!cost16) { g2w_x = -1.0; return; }
-    /* OR_2W_READ / OR_2W_PUB: cycles a cross-wave dependency adds to the consumer's update (its LDS
-     * read of the body) and to the producer's (the LDS write + flag), waiting or not */
-    g2w_read = getenv("OR_2W_READ") ? atof(getenv("OR_2W_READ")) : 0.0;
-    g2w_pub = getenv("OR_2W_PUB") ? atof(getenv("OR_2W_PUB")) : 0.0;
-    for (int i = 0; i < 16; ++i) g2w_cost[i] = cost16[i];
-    g2w_x = x; g2w_b = b;
-}
-static double twowave_run(const Solver* s, const int* dyn, int nb, unsigned mask, int sweeps, int iters, int barriers) {
-    double fin[256], tw[2] = {0.0, 0.0};
-    int own[256], n[2] = {0, 0};
-    for (int i = 0; i < s->count; ++i) ++n[(mask >> i) & 1u];
-    for (int k = 0; k < nb; ++k) { fin[k] = 0.0; own[k] = -1; }
-    int have = (iters & 3) == 2;
-    for (int r = 0; r < sweeps; ++r) {
-        for (int i = 0; i < s->count; ++i) {
-            const int w = (mask >> i) & 1u, ab[2] = {s->vcs[i].indexA, s->vcs[i].indexB};
-            double t = tw[w], rd = 0.0, pub = 0.0;
-            for (int j = 0; j < 2; ++j)
-                if (dyn[ab[j]] && own[ab[j]] >= 0) {
-                    const double ready = fin[ab[j]] + (own[ab[j]] != w ? g2w_x : 0.0);
-                    if (own[ab[j]] != w) rd = g2w_read;   /* the LDS read of a body the other wave wrote */
-                    if (ready > t) t = ready;
-                }
-            for (int j = 0; j < 2 && mask; ++j)   /* publishing a body the other wave updates next */
-                if (dyn[ab[j]]) {
-                    int nx = -1;
-                    for (int q = 1; q <= s->count && nx < 0; ++q) {
-                        const int k2 = (i + q) % s->count;
-                        if (s->vcs[k2].indexA == ab[j] || s->vcs[k2].indexB == ab[j]) nx = k2;
-                    }
-                    if (nx >= 0 && (int)((mask >> nx) & 1u) != w) pub = g2w_pub;
-                }
-            const int nw = n[w] < 8 ? n[w] : 8, p = s->vcs[i].pointCount < 2 ? 0 : 1;
-            t += rd + pub + g2w_cost[p * 8 + nw - 1];
-            tw[w] = t;
-            for (int j = 0; j < 2; ++j)
-                if (dyn[ab[j]]) { fin[ab[j]] = t; own[ab[j]] = w; }
-        }
-        if (!barriers) continue;
-        const int done = r + 1, left = iters - done, m = exit_mask(done);
-        if ((left & m) == 0 && have) {
-            const double t = (tw[0] > tw[1] ? tw[0] : tw[1]) + g2w_b;
-            tw[0] = tw[1] = t;
-        }
-        if ((left & m) == 2) have = 1;
-    }
-    return tw[0] > tw[1] ? tw[0] : tw[1];
-}
-/* Paired contact updates on one wave (b2o_model_dual): the island's Gauss-Seidel stream of
- * `D` sweeps (item q = sweep q / nc, contact q % nc) cut into slots of one or two updates run by one
- * instruction stream in two lanes.  Greedy, in stream order: a slot takes the first unscheduled item
- * u and the first unscheduled item v after it (at most `window` items on) with u's point count that
- * shares no dynamic body with u nor with any unscheduled item between them -- so every body and
- * every contact sees its updates in the sequential order and the result is bit-exact.  out[t] =
- * u | v << 4 (v == u: a single); returns the slot count (or -1 when `cap` is too small). */
-static int g_dual_mixed = 0;   /* model only: pairs of any point counts */
-int b2o_dual_schedule(int nc, const int* ia, const int* ib, const int* dyn, const int* pcount, int D, int window,
-                      unsigned char* out, int cap) {
-    const int n = nc * D;
-    unsigned char done[2048];
-    if (n > 2048 || nc > 15) return -1;
-    for (int q = 0; q < n; ++q) done[q] = 0;
-    int t = 0, u = 0;
-#define CONFL(p, q) ((dyn[ia[(p) % nc]] && (ia[(p) % nc] == ia[(q) % nc] || ia[(p) % nc] == ib[(q) % nc])) || \
-                     (dyn[ib[(p) % nc]] && (ib[(p) % nc] == ia[(q) % nc] || ib[(p) % nc] == ib[(q) % nc])))
-    while (u < n) {
-        done[u] = 1;
-        int v = u;
-        for (int q = u + 1; q < n && q <= u + window; ++q) {
-            if (done[q] || (!g_dual_mixed && pcount[q % nc] != pcount[u % nc]) || CONFL(u, q)) continue;
-            int ok = 1;
-            for (int r = u + 1; r < q && ok; ++r)
-                if (!done[r] && CONFL(r, q)) ok = 0;
-            if (ok) { v = q; break; }
-        }
-        done[v] = 1;
-        if (t >= cap) return -1;
-        out[t++] = (unsigned char)((u % nc) | ((v % nc) << 4));
-        while (u < n && done[u]) ++u;
-    }
-#undef CONFL
-    return t;
-}
-static double g_dual_factor = 0.0;
-static int g_dual_window = 0, g_dual_nodrain = 0;
-/* window < 0: |window|, and the stream never drains (the bound without early-exit meeting points) */
-void b2o_model_dual(double factor, int window) {
-    g_dual_factor = factor; g_dual_window = window < 0 ? -window : window; g_dual_nodrain = window < 0;
-    g_dual_mixed = getenv("OR_DUAL_MIXED") != NULL;
-}
-/* the sweeps as the paired path would run them: segments between the early-exit events (snapshot
- * and compare sweeps, where the stream drains), each slot priced as one update x factor */
-static double dual_run(const Solver* s, const int* dyn, int sweeps, int iters) {
-    const int nc = s->count;
-    int ia[16], ib[16], pc[16];
-    for (int i = 0; i < nc; ++i) { ia[i] = s->vcs[i].indexA; ib[i] = s->vcs[i].indexB; pc[i] = s->vcs[i].pointCount; }
-    unsigned char sl[2048];
-    double t = 0.0;
+/* The velocity sweeps, as b2Island::Solve calls b2ContactSolver::SolveVelocityConstraints `iters`
+ * times; returns the number of sweeps the device runs.  The device (mrp_world.h solver_velocity_*)
+ * snapshots the state two sweeps before every sweep k with iters - k = 0 (mod 4 up to sweep 32, mod
+ * 16 after; exit_mask), and once the state after k equals it the state has period 1 or 2, so the
+ * state after all `iters` sweeps is the state after k -- the same bits, fewer sweeps.  Three builds
+ * (Makefile): `port` runs all sweeps and captures nothing, the checker runs all sweeps and reports
+ * the device's count, `early` stops where the device does. */
+#ifndef OR_NO_WORK
+enum { SWEEP_CAPTURE = 1, SWEEP_STOP = 0 };
+#elif defined(OR_EARLY_EXIT)
+enum { SWEEP_CAPTURE = 1, SWEEP_STOP = 1 };
+#else
+enum { SWEEP_CAPTURE = 0, SWEEP_STOP = 0 };
+#endif
+/* the state the device compares: every contact's impulses, every island body's velocity */
+static void sweep_state(const Solver* s, int nbodies, float* dst) {
     int k = 0;
-    while (k < sweeps) {
-        int e = g_dual_nodrain ? sweeps : k + 1;   /* next event sweep (or the end) */
-        while (e < sweeps) {
-            const int left = iters - e, m = exit_mask(e);
-            if ((left & m) == 0 || (left & m) == 2) break;
-            ++e;
-        }
-        const int D = e - k;
-        const int ns = b2o_dual_schedule(nc, ia, ib, dyn, pc, D, g_dual_window, sl, 2048);
-        if (ns < 0) return -1.0;
-        for (int q = 0; q < ns; ++q) {
-            const int u = sl[q] & 15, p = pc[u] < 2 ? 0 : 1;
-            t += g2w_cost[p * 8 + (nc < 8 ? nc : 8) - 1] * g_dual_factor;
-        }
-        k = e;
-    }
-    return t;
+    for (int i = 0; i < s->count; ++i)
+        for (int j = 0; j < 2; ++j) { dst[k++] = s->vcs[i].points[j].normalImpulse; dst[k++] = s->vcs[i].points[j].tangentImpulse; }
+    for (int b = 0; b < nbodies; ++b) { dst[k++] = s->velocities[b].v.x; dst[k++] = s->velocities[b].v.y; dst[k++] = s->velocities[b].w; }
 }
-static void work_model_2wave(const Solver* s, const int* dyn, int sweeps, int iters, OrWork* k) {
-    if (g2w_x < 0.0 || s->count < 1) return;
-    if (g_dual_factor > 0.0) {   /* b2o_model_dual: vel_2wave holds the paired one-wave path */
-        const double one = twowave_run(s, dyn, 256, 0u, sweeps, iters, 0);
-        double d = s->count >= 3 && s->count <= 15 ? dual_run(s, dyn, sweeps, iters) : one;
-        if (d < 0.0) d = one;
-        k->vel_1wave += (long)(one + 0.5);
-        k->vel_2wave += (long)(d + 0.5);
-        return;
+static int velocity_sweeps(Solver* s, int iters, int nbodies) {
+    if (!SWEEP_CAPTURE) {
+        for (int it = 0; it < iters; ++it) solver_solve_velocity(s);
+        return iters;
     }
-    int nb = 0;
-    for (int i = 0; i < s->count; ++i) {
-        if (s->vcs[i].indexA + 1 > nb) nb = s->vcs[i].indexA + 1;
-        if (s->vcs[i].indexB + 1 > nb) nb = s->vcs[i].indexB + 1;
-    }
-    if (nb > 256) return;
-    const double one = twowave_run(s, dyn, nb, 0u, sweeps, iters, 0);
-    double two = one;
-    if (s->count >= 2 && s->count <= 12) {
-        unsigned best = 0u;
-        double bt = 0.0;
-        const int probe = sweeps < 8 ? sweeps : 8;
-        for (unsigned m = 0; m < (1u << (s->count - 1)); ++m) {
-            const unsigned mask = m << 1;   /* contact 0 stays on wave 0 */
-            const double t = twowave_run(s, dyn, nb, mask, probe, iters, 0);
-            if (m == 0 || t < bt) { bt = t; best = mask; }
-        }
-        two = twowave_run(s, dyn, nb, best, sweeps, iters, 1);
-        if (best == 0u || two > one) two = one;   /* a split that does not pay stays on one wave */
-    }
-    k->vel_1wave += (long)(one + 0.5);
-    k->vel_2wave += (long)(two + 0.5);
-}
-
-/* diagnostic (b2o_topo_diag(1); b2o_topo_diag(2) also records 1- and 2-contact islands): island
- * topologies of 3- and 4-contact islands, weighted by sweeps run:
- * per contact (A slot, B slot, point count) with body slots numbered by first appearance and static
- * bodies as slot 7; 64 distinct signatures kept */
-static int g_topo_diag = 0;
-static long g_topo_sig[64], g_topo_w[64];
-static void topo_record(const Solver* s, const Island* is, int sweeps) {
-    int slot[256], ns = 0;
-    for (int k = 0; k < 256; ++k) slot[k] = -1;
-    long sig = s->count;
-    for (int i = 0; i < s->count; ++i) {
-        const int ab[2] = {s->vcs[i].indexA, s->vcs[i].indexB};
-        int sl[2];
-        for (int j = 0; j < 2; ++j) {
-            const Body* b = is->bodies[ab[j]];
-            if (b->invMass == 0.0f && b->invI == 0.0f) { sl[j] = 7; continue; }
-            if (slot[ab[j]] < 0) slot[ab[j]] = ns++;
-            sl[j] = slot[ab[j]];
-        }
-        sig = sig * 1000 + sl[0] * 100 + sl[1] * 10 + s->vcs[i].pointCount;
-    }
-#pragma omp critical
-    {
-        int k = 0;
-        while (k < 64 && g_topo_w[k] && g_topo_sig[k] != sig) ++k;
-        if (k < 64) { g_topo_sig[k] = sig; g_topo_w[k] += sweeps * (long)s->count; }
-    }
-}
-/* b2o_topo_diag(3): print (stderr, first 60) the contact list of islands with >= 5 contacts that run
- * >= 100 sweeps: per contact "A-B/points", body slots by first appearance, static bodies as S */
-static int g_topo_printed = 0;
-static void topo_print(const Solver* s, const Island* is, int sweeps) {
-    char buf[512];
-    int slot[256], ns = 0, n = 0;
-    for (int k = 0; k < 256; ++k) slot[k] = -1;
-    n += snprintf(buf + n, sizeof(buf) - n, "nc %d sweeps %3d:", s->count, sweeps);
-    for (int i = 0; i < s->count && n < 480; ++i) {
-        const int ab[2] = {s->vcs[i].indexA, s->vcs[i].indexB};
-        char c[2];
-        for (int j = 0; j < 2; ++j) {
-            const Body* b = is->bodies[ab[j]];
-            if (b->invMass == 0.0f && b->invI == 0.0f) { c[j] = 'S'; continue; }
-            if (slot[ab[j]] < 0) slot[ab[j]] = ns++;
-            c[j] = (char)('0' + slot[ab[j]]);
-        }
-        n += snprintf(buf + n, sizeof(buf) - n, " %c-%c/%d", c[0], c[1], s->vcs[i].pointCount);
-    }
-#pragma omp critical
-    {
-        if (g_topo_printed < 100000) { fprintf(stderr, "%s\n", buf); ++g_topo_printed; }
-    }
-}
-void b2o_topo_diag(int on, long* sig64, long* w64) {
-    g_topo_printed = 0;
-    for (int k = 0; k < 64; ++k) { if (sig64) sig64[k] = g_topo_sig[k]; if (w64) w64[k] = g_topo_w[k]; }
-    if (on >= 0) { g_topo_diag = on; for (int k = 0; k < 64; ++k) { g_topo_sig[k] = 0; g_topo_w[k] = 0; } }
-}
-
-#ifdef OR_NO_WORK
-/* CPU-baseline builds (Makefile targets `fast` and `early`, bench.py cpu_baseline): the velocity
- * sweeps without the work model.  OR_EARLY_EXIT stops at the device's exact early exit
- * (mrp_world.h solver_velocity_*): a snapshot two sweeps before every sweep k with 180 - k = 0
- * (mod 4 up to sweep 32, mod 16 after), and once the state after k equals it the state has period
- * 1 or 2, so the state after
- * all `iters` sweeps is the state after k -- the same bits, fewer sweeps.  Without OR_EARLY_EXIT
- * all `iters` sweeps run, as b2ContactSolver::SolveVelocityConstraints is called by b2Island::Solve. */
-static void velocity_sweeps(Solver* s, int iters, int nbodies) {
-#ifdef OR_EARLY_EXIT
-    const int nc = s->count, ns = 4 * nc + 3 * nbodies;
+    const int ns = 4 * s->count + 3 * nbodies;
     float snap_st[512], cur_st[512];
     float* snap = ns <= 512 ? snap_st : (float*)malloc(sizeof(float) * (size_t)ns);
     float* cur = ns <= 512 ? cur_st : (float*)malloc(sizeof(float) * (size_t)ns);
-#define SWEEP_STATE(dst) do {                                                                      \
-        int k_ = 0;                                                                                \
-        for (int i_ = 0; i_ < nc; ++i_)                                                            \
-            for (int j_ = 0; j_ < 2; ++j_) {                                                       \
-                (dst)[k_++] = s->vcs[i_].points[j_].normalImpulse;                                 \
-                (dst)[k_++] = s->vcs[i_].points[j_].tangentImpulse;                                \
-            }                                                                                      \
-        for (int b_ = 0; b_ < nbodies; ++b_) {                                                     \
-            (dst)[k_++] = s->velocities[b_].v.x; (dst)[k_++] = s->velocities[b_].v.y;              \
-            (dst)[k_++] = s->velocities[b_].w;                                                     \
-        }                                                                                          \
-    } while (0)
-    int have = (iters & 3) == 2;
-    if (have) SWEEP_STATE(snap);
+    float* hist = b2w_history(ns, iters);
+    int have = (iters & 3) == 2, run = -1;
+    if (have) sweep_state(s, nbodies, snap);
+    if (hist) sweep_state(s, nbodies, hist);
     for (int it = 0; it < iters; ++it) {
         solver_solve_velocity(s);
-        /* the device's schedule (mrp_world.h exit_mask): every 4 sweeps up to sweep 32, then every 16 */
+        if (hist) sweep_state(s, nbodies, hist + (size_t)(it + 1) * ns);
+        if (run >= 0) continue;
         const int left = iters - (it + 1), m = exit_mask(it + 1);
         if ((left & m) == 0 && have) {
-            SWEEP_STATE(cur);
-            if (memcmp(cur, snap, sizeof(float) * (size_t)ns) == 0) break;
+            sweep_state(s, nbodies, cur);
+            if (memcmp(cur, snap, sizeof(float) * (size_t)ns) == 0) { run = it + 1; if (SWEEP_STOP) break; }
         }
-        if ((left & m) == 2) { SWEEP_STATE(snap); have = 1; }
+        if ((left & m) == 2) { sweep_state(s, nbodies, snap); have = 1; }
     }
-#undef SWEEP_STATE
+    if (hist) run = b2w_history_done(hist, ns, iters, s->count, run);
     if (snap != snap_st) free(snap);
     if (cur != cur_st) free(cur);
-#else
-    (void)nbodies;
-    for (int it = 0; it < iters; ++it) solver_solve_velocity(s);
-#endif
+    return run >= 0 ? run : iters;
 }
-#endif
 
 static void island_solve(Island* is, World* w, TimeStep step) {
     float h = step.dt;
@@ -1679,16 +1292,7 @@ static void island_solve(Island* is, World* w, TimeStep step) {
     solver_init(&s, step, is->contacts, is->contactCount, is->positions, is->velocities);
     solver_init_velocity_constraints(&s);
     if (step.warmStarting) solver_warm_start(&s);
-#ifdef OR_NO_WORK
-    velocity_sweeps(&s, step.velocityIterations, is->bodyCount);
-    solver_store_impulses(&s);
-    integrate_positions(is, h, 0);
-    for (int i = 0; i < step.positionIterations; ++i) {
-        w->posIters++;
-        if (solver_solve_position(&s, 0, -1, -1)) break;
-    }
-#else
-    const int sweeps = work_velocity_sweeps(&s, step.velocityIterations, is->bodyCount);
+    const int sweeps = velocity_sweeps(&s, step.velocityIterations, is->bodyCount);
     w->velIters += (long)step.velocityIterations * is->contactCount;
     solver_store_impulses(&s);
     integrate_positions(is, h, 0);
@@ -1698,26 +1302,7 @@ static void island_solve(Island* is, World* w, TimeStep step) {
         ++passes;
         if (solver_solve_position(&s, 0, -1, -1)) break;
     }
-    if (g_topo_diag && g_topo_diag < 3 && is->contactCount >= (g_topo_diag > 1 ? 1 : 3) && is->contactCount <= 4) topo_record(&s, is, sweeps);
-    if (g_topo_diag == 3 && is->contactCount >= 5 && sweeps >= 100) topo_print(&s, is, sweeps);
-    if (is->contactCount > 0) {
-        int dyn[256], lp = 0, pts = 0, n1 = 0, n2 = 0;
-        for (int k = 0; k < is->bodyCount && k < 256; ++k) dyn[k] = is->bodies[k]->invMass > 0.0f || is->bodies[k]->invI > 0.0f;
-        const int L = work_levels(&s, dyn, &lp);
-        for (int i = 0; i < s.count; ++i) { pts += s.pcs[i].pointCount; if (s.vcs[i].pointCount == 2) ++n2; else ++n1; }
-        OrWork* k = &w->work;
-        k->islands += 1; k->vel_sweeps += sweeps;
-        k->vel_upd1 += (long)sweeps * n1; k->vel_upd2 += (long)sweeps * n2; k->vel_levels += (long)sweeps * L;
-        k->pos_passes += passes; k->pos_points += (long)passes * pts; k->pos_level_points += (long)passes * lp;
-        k->vel_pipe += work_pipe(&s, dyn, sweeps, 0);
-        k->pos_pipe += work_pipe(&s, dyn, passes, 1);
-        work_model_2wave(&s, dyn, sweeps, step.velocityIterations, k);
-        const long units = (long)sweeps * s.count + (long)passes * pts;
-        k->isl_units += units;
-        w->stepIslSum += units;
-        if (units > w->stepIslMax) w->stepIslMax = units;
-    }
-#endif
+    b2w_island_solved(w, is, &s, sweeps, step.velocityIterations, passes);
     for (int i = 0; i < is->bodyCount; ++i) {
         Body* body = is->bodies[i];
         body->sweep.c = is->positions[i].c; body->sweep.a = is->positions[i].a;
@@ -1735,44 +1320,18 @@ static void island_solve_toi(Island* is, TimeStep sub, int toiIndexA, int toiInd
     }
     Solver s;
     solver_init(&s, sub, is->contacts, is->contactCount, is->positions, is->velocities);
-#ifdef OR_NO_WORK
-    (void)k;
-    for (int i = 0; i < sub.positionIterations; ++i)
-        if (solver_solve_position(&s, 1, toiIndexA, toiIndexB)) break;
-    is->bodies[toiIndexA]->sweep.c0 = is->positions[toiIndexA].c;
-    is->bodies[toiIndexA]->sweep.a0 = is->positions[toiIndexA].a;
-    is->bodies[toiIndexB]->sweep.c0 = is->positions[toiIndexB].c;
-    is->bodies[toiIndexB]->sweep.a0 = is->positions[toiIndexB].a;
-    solver_init_velocity_constraints(&s);
-    velocity_sweeps(&s, sub.velocityIterations, is->bodyCount);
-#else
     int passes = 0;
     for (int i = 0; i < sub.positionIterations; ++i) {
         ++passes;
         if (solver_solve_position(&s, 1, toiIndexA, toiIndexB)) break;
     }
-    {   /* work model: in the TOI position passes only the TOI pair moves */
-        int dyn[256], lp = 0, pts = 0;
-        for (int q = 0; q < is->bodyCount && q < 256; ++q) dyn[q] = q == toiIndexA || q == toiIndexB;
-        work_levels(&s, dyn, &lp);
-        for (int i = 0; i < s.count; ++i) pts += s.pcs[i].pointCount;
-        k->toi_pos_points += (long)passes * pts; k->toi_pos_level_points += (long)passes * lp;
-        k->pos_pipe += work_pipe(&s, dyn, passes, 1);
-    }
+    b2w_toi_positions(k, is, &s, toiIndexA, toiIndexB, passes);
     is->bodies[toiIndexA]->sweep.c0 = is->positions[toiIndexA].c;
     is->bodies[toiIndexA]->sweep.a0 = is->positions[toiIndexA].a;
     is->bodies[toiIndexB]->sweep.c0 = is->positions[toiIndexB].c;
     is->bodies[toiIndexB]->sweep.a0 = is->positions[toiIndexB].a;
     solver_init_velocity_constraints(&s);
-    const int sweeps = work_velocity_sweeps(&s, sub.velocityIterations, is->bodyCount);
-    {
-        int dyn[256];
-        for (int q = 0; q < is->bodyCount && q < 256; ++q) dyn[q] = is->bodies[q]->invMass > 0.0f || is->bodies[q]->invI > 0.0f;
-        const int L = work_levels(&s, dyn, NULL);
-        k->toi_vel_upd += (long)sweeps * s.count; k->toi_vel_levels += (long)sweeps * L;
-        k->vel_pipe += work_pipe(&s, dyn, sweeps, 0);
-    }
-#endif
+    b2w_toi_sweeps(k, is, &s, velocity_sweeps(&s, sub.velocityIterations, is->bodyCount));
     integrate_positions(is, sub.dt, 1);
     solver_free(&s);
 }
@@ -2232,7 +1791,6 @@ static void world_solve_toi(World* w, TimeStep step) {
 }
 
 void b2o_step(World* w, float dt, int velIters, int posIters) {
-    w->stepIslSum = 0; w->stepIslMax = 0;
     if (w->flags & WF_NEWFIXTURE) { cm_find_new_contacts(&w->cm); w->flags &= ~WF_NEWFIXTURE; }
     w->flags |= WF_LOCKED;
     TimeStep step;
@@ -2249,5 +1807,5 @@ void b2o_step(World* w, float dt, int velIters, int posIters) {
         for (Body* b = w->bodyList; b; b = b->next) { b->force = v2(0.0f, 0.0f); b->torque = 0.0f; }
     }
     w->flags &= ~WF_LOCKED;
-    w->work.isl_concurrent_save += w->stepIslSum - w->stepIslMax;
+    b2w_step_done(w);
 }

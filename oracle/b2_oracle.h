@@ -106,7 +106,7 @@ typedef struct {
     ContactCb begin, end; void* listenerCtx;   /* NULL begin/end == no listener */
 } ContactManager;
 
-/* Work model (test infrastructure, tools/chain_model.py): the serial solver work one lane's
+/* Work model (b2_work.c; test infrastructure, tools/chain_model.py): the serial solver work one lane's
  * step carries as the device runs it -- velocity sweeps counted with the device's exact early exit
  * (mrp_world.h solver_velocity_*: state after sweep k equals the state after k-2) -- and the same
  * work grouped into dependency levels (consecutive Gauss-Seidel contacts whose dynamic bodies are
@@ -168,25 +168,6 @@ Fixture* b2o_create_fixture(Body* b, const FixtureDef* def);
 void b2o_destroy_body(World* w, Body* b);
 void b2o_step(World* w, float dt, int velIters, int posIters);
 void b2o_set_listener(World* w, ContactCb begin, ContactCb end, void* ctx);
-
-/* diagnostic: period histogram of the islands whose velocity sweeps never reach period 1 or 2
- * (see b2_oracle.c); on >= 0 resets and sets the switch, out300 (may be NULL) receives it */
-void b2o_period_diag(int on, long* out300);
-/* diagnostic: the work model counts velocity sweeps as if periods up to p were detected (0 = the device) */
-void b2o_model_period(int p);
-/* diagnostic: price the velocity sweeps on one wave and split over two (OrWork vel_1wave /
- * vel_2wave); cost[(p - 1) * 8 + n - 1] = cycles of one p-point contact update on a wave holding n
- * contacts (n > 8 priced as 8), x = cycles of one cross-wave handoff, b = cycles of the two waves'
- * joint early-exit compare; cost NULL switches the model off */
-void b2o_model_2wave(const double* cost16, double x, double b);
-/* diagnostic: with factor > 0, vel_2wave prices the paired one-wave path instead (slots of one or two
- * same-point-count updates, b2o_dual_schedule, each priced as one update x factor); 0 switches it off */
-void b2o_model_dual(double factor, int window);
-/* the paired path's slot schedule of D sweeps of an nc-contact island (see b2_oracle.c) */
-int b2o_dual_schedule(int nc, const int* ia, const int* ib, const int* dyn, const int* pcount, int D, int window,
-                      unsigned char* out, int cap);
-/* diagnostic: topology histogram of 3- and 4-contact islands (see b2_oracle.c) */
-void b2o_topo_diag(int on, long* sig64, long* w64);
 
 /* body API used by the env layer (pybox2d semantics) */
 void b2o_set_linear_velocity(Body* b, V2 v);

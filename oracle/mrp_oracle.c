@@ -698,6 +698,7 @@ void or_capacity(const OrEnv* e, int* out8) {
 void or_work(const OrEnv* e, long* out20) {
     OrWork k = e->world->work;
     k.sat_calls = e->world->cm.satCalls;
+    _Static_assert(sizeof(OrWork) == 20 * sizeof(long), "or_work copies OrWork as 20 longs (oracle.py WORK_NAMES)");
     const long* v = (const long*)&k;
     for (int i = 0; i < 20; ++i) out20[i] = v[i];
 }

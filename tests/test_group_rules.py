@@ -163,7 +163,7 @@ def test_branch_free_block_solver_equals_case_loop():
 
 # ----------------------------------------------------------------------------- paired-slot schedule
 def test_dual_schedule_keeps_every_body_in_sequential_order():
-    """b2o_dual_schedule (the paired-update model of the 3-block accounting, oracle/b2_oracle.c):
+    """b2o_dual_schedule (the paired-update model of the 3-block accounting, oracle/b2_work.c):
     replaying its slots must give every dynamic body the same sequence of updates, and every contact
     its sweeps in order, as the Gauss-Seidel stream; a slot's two updates never share a dynamic body
     and have one point count."""

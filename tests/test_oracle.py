@@ -416,6 +416,25 @@ def test_work_model_is_consistent(oracle_lib):
         assert table[key]["flops_per_launch"] > 0 and table[key]["latency_floor_ms"] > 0
 
 
+def test_work_model_matches_pinned_counts(oracle_lib):
+    """The checker's work model (oracle/b2_work.c) gives exactly the counts pinned in
+    tests/golden/work_model.npz (make_golden.py work_model_record, replayed here): the OrWork array of
+    env ids 0, 1, 2, 4, 5, the two-wave and paired-update cycle sums, the sweep total under
+    b2o_model_period(8), and on one thread the block-solver case counts and the period and topology
+    histograms of env 0 and 4.  With every switch back off the first array comes out again."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    rec = gen.work_model_record(threads=min(8, os.cpu_count() or 1))
+    for e in gen.WORK_ENVS:
+        assert np.array_equal(rec.pop(f"again_{e}"), rec[f"work_{e}"]), f"env {e}: a model switch stayed on"
+    with np.load(os.path.join(GOLDEN, "work_model.npz")) as pin:
+        assert sorted(pin.files) == sorted(rec)
+        for k in pin.files:
+            assert np.array_equal(rec[k], pin[k]), k
+
+
 @pytest.mark.parametrize("env_id", [0, 1, 2, 4, 5])
 def test_baseline_builds_bit_identical(orc, env_id):
     """bench.py's CPU baseline times two builds of the oracle without the work model (oracle/Makefile:

@@ -1,7 +1,7 @@
 """Serial-chain model of k_step (analysis; CPU only): how long each launch's slowest lane takes,
-from the oracle's work counts (oracle/b2_oracle.h OrWork: velocity sweeps counted with the
-device's exact early exit, position point updates, TOI events), and how much of it grouping each
-island's Gauss-Seidel order into dependency levels would remove.
+from the oracle's work counts (oracle/b2_work.c, OrWork in oracle/b2_oracle.h: velocity sweeps
+counted with the device's exact early exit, position point updates, TOI events), and how much of it
+grouping each island's Gauss-Seidel order into dependency levels would remove.
 
     python tools/chain_model.py [env] [lanes] [first_step] [last_step] [kernel_trace.csv warmup]
 

@@ -1,6 +1,6 @@
 """VALU and latency rooflines of k_step from the oracle's op counts (CPU only).
 
-The oracle (oracle/b2_oracle.c, work model OrWork) counts, for every lane and launch of the exact
+The oracle (work model OrWork, oracle/b2_work.c) counts, for every lane and launch of the exact
 bench.py workload (seed, lanes, step window), the solver work the device runs: velocity contact
 updates by point count (sweeps counted with the device's exact early exit), position point
 updates, narrow-phase polygon pairs, b2TimeOfImpact calls and TOI islands.  Each unit is priced

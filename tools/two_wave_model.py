@@ -4,7 +4,7 @@ per world would use idle slots.)
 
     python tools/two_wave_model.py VELBENCH_TXT XCHBENCH_TXT [env] [lanes] [first_step] [last_step]
 
-The oracle's work model (b2o_model_2wave, oracle/b2_oracle.c) replays every island's Gauss-Seidel
+The oracle's work model (b2o_model_2wave, oracle/b2_work.c) replays every island's Gauss-Seidel
 order with the device's exact sweep count and prices it (a) on one wave and (b) split over two waves
 with the best contact partition: each wave keeps the sequential order of its contacts, a contact
 waits for the previous update of each dynamic body it touches (+ one LDS handoff when that update
