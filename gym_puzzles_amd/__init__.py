@@ -7,6 +7,7 @@ gym_puzzles env interface.  See DESIGN.md.
     MultiRobotPuzzleVecEnv SB3-style vectorised env with on-device auto-reset
     MultiRobotPuzzleVecNormalize / DeviceVecNormalize
                            SB3 VecNormalize + Monitor statistics on the device
+    pixels                 the numpy restatement of the pixel observations (Batch.pixels, obs_type="image")
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
 

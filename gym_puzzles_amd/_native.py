@@ -34,7 +34,7 @@ EXPORTED = (
     "mrp_set_time_limit", "mrp_selftest_sincos", "mrp_debug_stamps", "mrp_debug_stamps_ext",
     "mrp_debug_trace", "mrp_debug_trace_words", "mrp_debug_progress", "mrp_debug_velbench", "mrp_debug_posbench", "mrp_norm_create", "mrp_norm_destroy", "mrp_norm_last_error", "mrp_norm_set_stream",
     "mrp_norm_set_training", "mrp_norm_set_norm_obs", "mrp_norm_reset_device", "mrp_norm_step_device", "mrp_norm_step_device_ex", "mrp_norm_get_stats", "mrp_norm_set_stats",
-    "mrp_render", "mrp_render_device", "mrp_get_goals", "mrp_shapes",
+    "mrp_render", "mrp_render_device", "mrp_get_goals", "mrp_shapes", "mrp_pixels", "mrp_pixels_device",
 )
 
 _lib = None
@@ -92,6 +92,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     L.mrp_selftest_sincos.argtypes = [i, P, P, P, i]
     L.mrp_render.argtypes = [P, P, i, i, i, P]
     L.mrp_render_device.argtypes = [P, P, i, i, i, P]
+    L.mrp_pixels.argtypes = [P, i, i, i, i, P, P, P]
+    L.mrp_pixels_device.argtypes = [P, i, i, i, i, P, P, P]
     L.mrp_get_goals.argtypes = [P, P]
     L.mrp_shapes.argtypes = [i, P, P, P, P]
     L.mrp_debug_stamps.argtypes = [i, P]
@@ -332,6 +334,31 @@ class Batch:
     def render_device(self, d_lanes_ptr: int, n: int, width: int, height: int, d_rgb_ptr: int):
         """Asynchronous render into a device buffer (e.g. a torch uint8 tensor's data_ptr())."""
         self._check(load().mrp_render_device(self._h, ctypes.c_void_p(d_lanes_ptr), n, width, height, ctypes.c_void_p(d_rgb_ptr)))
+
+    def pixels_device(self, width: int, height: int, channels: int, depth: int, d_done_ptr, d_prev_ptr, d_next_ptr: int):
+        """Asynchronous frame-stack update of every lane on device pointers (mrp_pixels_device):
+        uint8 [n_lanes, depth, height, width, channels] ``next`` from ``prev`` (0 / None: fresh stacks)
+        and the lanes' current state; lanes whose ``done`` byte (0 / None: none) is set start afresh."""
+        ptr = (lambda a: ctypes.c_void_p(a) if a else None)
+        self._check(load().mrp_pixels_device(self._h, int(width), int(height), int(channels), int(depth), ptr(d_done_ptr),
+                                             ptr(d_prev_ptr), ptr(d_next_ptr)))
+
+    def pixels(self, width: int, height: int, channels: int = 3, depth: int = 1, done=None, prev=None) -> np.ndarray:
+        """Pixel observations of every lane (mrp_pixels): uint8 [n_lanes, depth*height, width, channels],
+        ``depth`` frames stacked vertically, oldest first; the newest is the frame of the lane's current
+        state (RGB, or the integer luma with channels=1).  ``prev``: the stack this call returned last
+        (None: a fresh episode, older frames zero); ``done`` [n_lanes]: lanes that start afresh.
+        The numpy restatement of the rule is gym_puzzles_amd.pixels.advance."""
+        shape = (self.n_lanes, int(depth) * int(height), int(width), int(channels))
+        d = None if done is None else np.ascontiguousarray(done, np.uint8).reshape(self.n_lanes)
+        if prev is not None:
+            if prev.shape != shape or prev.dtype != np.uint8:
+                raise ValueError(f"prev: expected uint8 {shape}, got {prev.dtype} {prev.shape}")
+            prev = np.ascontiguousarray(prev)
+        # sizes the library refuses (MrpError below) never reach the kernel: any buffer will do for them
+        out = np.zeros(shape if min(shape) > 0 and depth <= 16 else (1,), np.uint8)
+        self._check(load().mrp_pixels(self._h, int(width), int(height), int(channels), int(depth), _p(d), _p(prev), _p(out)))
+        return out
 
     def set_state(self, state: np.ndarray):
         s = np.ascontiguousarray(state, np.uint32)

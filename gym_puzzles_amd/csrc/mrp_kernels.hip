@@ -697,6 +697,64 @@ int mrp_render(mrp_ctx* ctx, const int32_t* lanes, int n, int width, int height,
     return rc;
 }
 
+// ------------------------------------------------------------------------------ pixel observations
+// the argument checks shared by mrp_pixels_device and mrp_pixels (no HIP call: a null ctx is refused
+// on a machine without a device too)
+static int pixels_args(mrp_ctx* ctx, int W, int H, int C, int depth, const uint8_t* prev, const uint8_t* next,
+                       mrpr::RenderArgs& A) {
+    if (!ctx) { g_create_error = "mrp_pixels: null context"; return MRP_E_ARG; }
+    if (!next) { ctx->err = "mrp_pixels: null output"; return MRP_E_ARG; }
+    if (C != 1 && C != 3) { ctx->err = "mrp_pixels: channels must be 1 (luma) or 3 (RGB)"; return MRP_E_ARG; }
+    if (depth < 1 || depth > 16) { ctx->err = "mrp_pixels: depth must be 1..16"; return MRP_E_ARG; }
+    if (!ctx->have_reset) { ctx->err = "mrp_pixels: call mrp_reset first"; return MRP_E_STATE; }
+    if (render_args(ctx, W, H, A) != MRP_OK) { ctx->err = "mrp_pixels: bad image size"; return MRP_E_ARG; }
+    if (depth > 1 && prev == next) { ctx->err = "mrp_pixels: prev and next must be different buffers when depth > 1"; return MRP_E_ARG; }
+    return MRP_OK;
+}
+
+int mrp_pixels_device(mrp_ctx* ctx, int width, int height, int channels, int depth, const uint8_t* d_done,
+                      const uint8_t* d_prev, uint8_t* d_next) {
+    mrpr::RenderArgs A;
+    const int rc = pixels_args(ctx, width, height, channels, depth, d_prev, d_next, A);
+    if (rc != MRP_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    dim3 grid((unsigned)ctx->n_lanes, (unsigned)((width * height + mrpr::PIX_CHUNK - 1) / mrpr::PIX_CHUNK));
+    env_ops(ctx->env_id)->pixels(ctx->stream, grid, ctx->d_state, ctx->n_lanes, width, height, channels, depth, A, d_done,
+                                 d_prev, d_next);
+    HIPCHK(ctx, hipGetLastError());
+    return MRP_OK;
+}
+
+int mrp_pixels(mrp_ctx* ctx, int width, int height, int channels, int depth, const uint8_t* done, const uint8_t* prev,
+               uint8_t* next) {
+    mrpr::RenderArgs A;
+    int rc = pixels_args(ctx, width, height, channels, depth, prev, next, A);
+    if (rc != MRP_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nl = (size_t)ctx->n_lanes, bytes = nl * depth * width * height * channels;
+    uint8_t *dd = nullptr, *dp = nullptr, *dn = nullptr;
+    rc = MRP_E_HIP;
+    bool ok = hipMalloc(&dn, bytes) == hipSuccess;
+    if (ok && done)
+        ok = hipMalloc(&dd, nl) == hipSuccess && hipMemcpyAsync(dd, done, nl, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok && prev && depth > 1)
+        ok = hipMalloc(&dp, bytes) == hipSuccess && hipMemcpyAsync(dp, prev, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok) {
+        rc = mrp_pixels_device(ctx, width, height, channels, depth, dd, dp, dn);
+        if (rc == MRP_OK) {
+            rc = MRP_E_HIP;
+            if (hipMemcpyAsync(next, dn, bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                hipStreamSynchronize(ctx->stream) == hipSuccess)
+                rc = MRP_OK;
+        }
+    }
+    if (rc == MRP_E_HIP && ctx->err.empty()) ctx->err = "mrp_pixels: HIP allocation/copy failed";
+    if (dd) (void)hipFree(dd);
+    if (dp) (void)hipFree(dp);
+    if (dn) (void)hipFree(dn);
+    return rc;
+}
+
 int mrp_get_goals(mrp_ctx* ctx, double* out) {
     if (!ctx || !out) return MRP_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));

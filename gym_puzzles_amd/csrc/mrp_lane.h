@@ -592,6 +592,10 @@ struct Launch {
                        const mrpr::RenderArgs& A, uint8_t* rgb) {
         hipLaunchKernelGGL(mrpr::k_render<ENV>, grid, dim3(mrpr::RBLOCK), 0, s, state, lanes, nl, W, H, A, rgb);
     }
+    static void pixels(hipStream_t s, dim3 grid, const uint32_t* state, int nl, int W, int H, int C, int depth,
+                       const mrpr::RenderArgs& A, const uint8_t* done, const uint8_t* prev, uint8_t* next) {
+        hipLaunchKernelGGL(mrpr::k_pixels<ENV>, grid, dim3(mrpr::PIX_BLOCK), 0, s, state, nl, W, H, C, depth, A, done, prev, next);
+    }
     static void goals(hipStream_t s, const uint32_t* state, int nl, double* out) {
         hipLaunchKernelGGL(mrpr::k_goals<ENV>, dim3((nl + 255) / 256), dim3(256), 0, s, state, nl, out);
     }
@@ -624,7 +628,7 @@ struct Launch {
         return EnvOps{lane_words<ENV>(), (int)(offsetof(LS, toiEvents) / 4),
                       {D::OBS, D::ACT, D::NDRAW, D::NA, D::NB, D::NF},
                       StateIO<ENV>::P, LS::C, LS::NCA, StateIO<ENV>::HWW, MRP_STEP_WAVES_PER_EU, upload_tables, init, reset, step,
-                      bodies, faults, counters, render, goals, debug_read, debug_progress};
+                      bodies, faults, counters, render, pixels, goals, debug_read, debug_progress};
     }
 };
 

@@ -22,6 +22,7 @@ struct RenderArgs {
 };
 constexpr int RBLOCK = 256;
 constexpr int RPPT = 8;        // pixels per thread: one display-list build serves RBLOCK*RPPT pixels
+constexpr int PIX_BLOCK = 256, PIX_CHUNK = 16384;   // k_pixels: threads per workgroup, pixels per workgroup (mrp_pixels.h)
 }  // namespace mrpr
 
 namespace mrp {
@@ -71,6 +72,9 @@ struct EnvOps {
     void (*counters)(hipStream_t, const uint32_t* state, int nl, int64_t* out /* [CTR_N] */);
     void (*render)(hipStream_t, dim3 grid, const uint32_t* state, const int32_t* lanes, int nl, int W, int H,
                    const mrpr::RenderArgs& A, uint8_t* rgb);
+    // the next frame stack of every lane (mrp_pixels_device; grid: lanes x chunks of the frame)
+    void (*pixels)(hipStream_t, dim3 grid, const uint32_t* state, int nl, int W, int H, int C, int depth,
+                   const mrpr::RenderArgs& A, const uint8_t* done, const uint8_t* prev, uint8_t* next);
     void (*goals)(hipStream_t, const uint32_t* state, int nl, double* out);
     // diagnostic builds only (MRP_E_STATE-like hipErrorNotSupported otherwise): copy `bytes` of
     // symbol `what` into `out` and zero it; point the progress word array at `dev_words`

@@ -191,3 +191,5 @@ __global__ void k_goals(const uint32_t* __restrict__ state, int nl, double* out)
 }
 
 }  // namespace mrpr
+
+#include "mrp_pixels.h"   // k_pixels: the frame-stack observation kernel over this display list

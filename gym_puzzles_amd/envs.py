@@ -29,6 +29,7 @@ import numpy as np
 
 from ._native import (STATUS_AGENT_OOB, STATUS_BLOCK_OOB, STATUS_FAULT, STATUS_KIND_MASK, STATUS_NONFINITE,
                       STATUS_PUZZLE_COMPLETE, Batch)
+from .pixels import stack_shape
 from .seeding import make_box, np_random
 from .spawn import ENV_VERSION, V2_AGENT_IDS, V3_AGENT_IDS, reference_draws
 
@@ -53,8 +54,7 @@ class _MRPBase:
         self.done_status = None
         self._params_updated = False
         self.set_reward_params()
-        low, high = self._obs_bounds()
-        self.observation_space = make_box(low, high, dtype=np.float32)
+        self.observation_space = self._obs_space()
         self.action_space = make_box(-np.ones(self._b.act_dim), np.ones(self._b.act_dim), dtype=np.float32)
         self.reset()
 
@@ -153,6 +153,10 @@ class _MRPBase:
     def _obs_bounds(self):
         return -self._obs_high(), self._obs_high()
 
+    def _obs_space(self):
+        low, high = self._obs_bounds()
+        return make_box(low, high, dtype=np.float32)
+
     @property
     def blks_in_place(self):
         return int(self._b.flags()[0, -1])
@@ -169,17 +173,46 @@ class _MRPBase:
 
 
 class MultiRobotPuzzle(_MRPBase):
-    """multi_robot_puzzle_00.py:142 (2 agents, light T block)."""
+    """multi_robot_puzzle_00.py:142 (2 agents, light T block).
+
+    A subclass that sets ``obs_type = 'image'`` (the reference's class attribute, :148) gets pixel
+    observations: ``observation_space`` is the uint8 box ``(480 * obs_depth, 640, 3)`` (:197-199),
+    ``frameskip`` world steps run per env step (:161), and ``reset()`` / ``step()`` return
+    ``obs_depth`` full-viewport RGB frames stacked vertically, newest at the bottom, drawn by the GPU
+    renderer (``mrp_pixels``).  The reference's own ``step()`` never fills its image state (it
+    returns the low-dim vector whatever ``obs_type`` says), so the stack rule is this build's
+    definition (``gym_puzzles_amd.pixels.advance``: ``reset()`` starts from zeros, every ``step()``
+    moves the frames up by one) and parity with the reference is unpinned."""
     env_id = 0
     obs_type = "low-dim"
     heavy = False
 
     def __init__(self, obs_depth=3, frameskip=4, device: int = 0):
-        if self.obs_type != "low-dim":
-            raise NotImplementedError("image observations need the renderer (SURVEY.md 8f-3)")
+        if self.obs_type not in ("low-dim", "image"):
+            raise ValueError(f"obs_type={self.obs_type!r}: 'low-dim' or 'image'")
         self._obs_depth = obs_depth
-        self.frameskip = 1          # low-dim obs: frameskip 1 (:161-162)
+        # low-dim obs: frameskip 1; image obs: the constructor argument (:161-162)
+        self.frameskip = int(frameskip) if self.obs_type == "image" else 1
+        self._stack = None
         super().__init__(device)
+
+    def _obs_space(self):
+        if self.obs_type == "image":
+            return make_box(0, 255, shape=stack_shape(640, 480, 3, self._obs_depth), dtype=np.uint8)
+        return super()._obs_space()
+
+    def _image(self, fresh: bool):
+        prev = None if fresh or self._stack is None else self._stack[None]
+        self._stack = self._b.pixels(640, 480, 3, self._obs_depth, prev=prev)[0]
+        return self._stack.copy()
+
+    def reset(self):
+        obs = super().reset()
+        return self._image(True) if self.obs_type == "image" else obs
+
+    def step(self, action):
+        obs, reward, done, info = super().step(action)
+        return (self._image(False) if self.obs_type == "image" else obs), reward, done, info
 
     def _obs_high(self):
         a = [np.inf] * 4 * self._b.n_agents

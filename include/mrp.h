@@ -181,6 +181,21 @@ int mrp_set_state(mrp_ctx* ctx, const uint32_t* in);
  * asynchronous on the ctx stream; plain: host pointers, synchronous. */
 int mrp_render_device(mrp_ctx* ctx, const int32_t* d_lanes, int n, int width, int height, uint8_t* d_rgb);
 int mrp_render(mrp_ctx* ctx, const int32_t* lanes, int n, int width, int height, uint8_t* rgb);
+/* Pixel observations ('image' obs_type, multi_robot_puzzle_00.py:148-162,197-200): the next frame
+ * stack of every lane.  next/prev: uint8 [n_lanes][depth][height][width][channels].
+ * Per lane, slot depth-1 (the newest) is the frame of the lane's current state, drawn by the
+ * rasteriser of mrp_render at width x height: channels 3 stores R, G, B, channels 1 the integer luma
+ * (77 R + 150 G + 29 B + 128) >> 8.  Slot k < depth-1 is slot k+1 of `prev`; with prev NULL, or for a
+ * lane whose `done` byte is nonzero (NULL: none), those slots are zero, as the reference starts an
+ * episode's image state from zeros.  The slots are stacked vertically, oldest first: a lane's block
+ * read as [depth*height][width][channels] is the observation.  One launch covers all lanes.
+ * MRP_E_ARG: channels not 1 or 3, depth outside 1..16, a size mrp_render refuses, a null ctx or
+ * next, prev == next with depth > 1 (the shift is not done in place); MRP_E_STATE before the first
+ * reset.  _device: device pointers, asynchronous on the ctx stream; plain: host pointers, synchronous. */
+int mrp_pixels_device(mrp_ctx* ctx, int width, int height, int channels, int depth,
+                      const uint8_t* d_done, const uint8_t* d_prev, uint8_t* d_next);
+int mrp_pixels(mrp_ctx* ctx, int width, int height, int channels, int depth,
+               const uint8_t* done, const uint8_t* prev, uint8_t* next);
 /* per lane block_final_pos (x, y, angle) per block, in the units of the reference's
  * block_final_pos (v0 px, v2 scaled units): double [n_lanes][n_blocks][3] */
 int mrp_get_goals(mrp_ctx* ctx, double* out);
