@@ -8,6 +8,8 @@ gym_puzzles env interface.  See DESIGN.md.
     MultiRobotPuzzleVecNormalize / DeviceVecNormalize
                            SB3 VecNormalize + Monitor statistics on the device
     pixels                 the numpy restatement of the pixel observations (Batch.pixels, obs_type="image")
+    DeviceRolloutBuffer    SB3 RolloutBuffer on the device: TimeLimit bootstrap + GAE in one launch
+                           (rollout.gae_device; rollout.gae_ref is the numpy restatement of the rule)
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
 
@@ -21,4 +23,7 @@ def __getattr__(name):
     if name in ("MultiRobotPuzzleVecEnv", "MultiRobotPuzzleVecNormalize", "DeviceVecNormalize"):
         from . import vec_env
         return getattr(vec_env, name)
+    if name == "DeviceRolloutBuffer":
+        from . import rollout
+        return rollout.DeviceRolloutBuffer
     raise AttributeError(name)

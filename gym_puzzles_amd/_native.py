@@ -34,7 +34,7 @@ EXPORTED = (
     "mrp_set_time_limit", "mrp_selftest_sincos", "mrp_debug_stamps", "mrp_debug_stamps_ext",
     "mrp_debug_trace", "mrp_debug_trace_words", "mrp_debug_progress", "mrp_debug_velbench", "mrp_debug_posbench", "mrp_norm_create", "mrp_norm_destroy", "mrp_norm_last_error", "mrp_norm_set_stream",
     "mrp_norm_set_training", "mrp_norm_set_norm_obs", "mrp_norm_reset_device", "mrp_norm_step_device", "mrp_norm_step_device_ex", "mrp_norm_get_stats", "mrp_norm_set_stats",
-    "mrp_render", "mrp_render_device", "mrp_get_goals", "mrp_shapes", "mrp_pixels", "mrp_pixels_device",
+    "mrp_gae_device", "mrp_render", "mrp_render_device", "mrp_get_goals", "mrp_shapes", "mrp_pixels", "mrp_pixels_device",
 )
 
 _lib = None
@@ -110,6 +110,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     L.mrp_norm_step_device_ex.argtypes = [P] * 11
     L.mrp_norm_get_stats.argtypes = [P, P]
     L.mrp_norm_set_stats.argtypes = [P, P]
+    L.mrp_gae_device.argtypes = [i, P, i, i, P, P, P, P, P, P, P, d, d, P, P]
     # every build exports the whole ABI of include/mrp.h (the diagnostics answer MRP_E_STATE outside
     # their -D builds), so an A/B library must be built from this ABI too: a missing symbol raises here
     L.mrp_debug_stamps_ext.argtypes = [i, P, P, P]

@@ -141,6 +141,103 @@ __global__ __launch_bounds__(NT) void k_apply(const float* __restrict__ obs, con
     ep_ret[l] = er; ep_len[l] = el;
 }
 
+// ---- k_gae: SB3 RolloutBuffer.compute_returns_and_advantage + the TimeLimit bootstrap --------------
+// The rule is gym_puzzles_amd/rollout.py's gae_ref (DESIGN.md "Rollout buffer"), numpy's dtype
+// promotion included: the recurrence's accumulator L is float64, each row's delta is float32 except
+// on the last row, and every product and sum rounds on its own (-ffp-contract=off).
+//
+// One thread per lane walks the rows from T-1 down to 0; a wave reads 64 consecutive elements of a
+// row.  The recurrence cannot be re-associated (the result is pinned bit for bit), but only L is
+// carried: the loads depend on nothing, so the rows are taken GAE_ROWS at a time and the loads of
+// the block below are issued before the chain of the block in hand runs.  Row s needs v[s+1] and
+// episode_starts[s+1], which the row above it already loaded, so each element is read once.
+constexpr int GAE_NT = 64;    // one wave per workgroup: 4096 lanes spread over 64 CUs
+constexpr int GAE_ROWS = 8;
+
+struct GaeRow { float r, v, tv; uint8_t es, tr; };
+
+template <bool BOOT>
+__device__ __forceinline__ GaeRow gae_load(size_t i, const float* __restrict__ rew, const float* __restrict__ val,
+                                           const uint8_t* __restrict__ es, const uint8_t* __restrict__ trunc,
+                                           const float* __restrict__ tval) {
+    GaeRow x;
+    x.r = rew[i]; x.v = val[i]; x.es = es[i];
+    x.tr = BOOT ? trunc[i] : (uint8_t)0;
+    x.tv = BOOT ? tval[i] : 0.0f;
+    return x;
+}
+
+// collect_rollouts: rewards[idx] += gamma * terminal_value, float32 throughout
+template <bool BOOT>
+__device__ __forceinline__ float gae_reward(const GaeRow& x, float g32) {
+    if (BOOT && x.tr) return x.r + g32 * x.tv;
+    return x.r;
+}
+
+// a row below the last: float32 delta, float64 accumulator; then this row becomes the "next" one
+template <bool BOOT>
+__device__ __forceinline__ void gae_row(const GaeRow& x, size_t i, float g32, float c32, double& L, float& nv, float& nnt,
+                                        float* __restrict__ adv, float* __restrict__ ret) {
+    const float delta = (gae_reward<BOOT>(x, g32) + (g32 * nv) * nnt) - x.v;
+    L = (double)delta + (double)(c32 * nnt) * L;
+    const float a = (float)L;
+    adv[i] = a;
+    ret[i] = a + x.v;
+    nv = x.v;
+    nnt = 1.0f - (x.es ? 1.0f : 0.0f);
+}
+
+template <bool BOOT>
+__global__ __launch_bounds__(GAE_NT) void k_gae(int T, int N, const float* __restrict__ rew, const float* __restrict__ val,
+                                                const uint8_t* __restrict__ es, const uint8_t* __restrict__ trunc,
+                                                const float* __restrict__ tval, const float* __restrict__ last_val,
+                                                const uint8_t* __restrict__ last_done, float g32, float c32,
+                                                float* __restrict__ adv, float* __restrict__ ret) {
+    const int lane = blockIdx.x * GAE_NT + threadIdx.x;
+    if (lane >= N) return;
+    const size_t n = (size_t)N;
+    const size_t top = (size_t)(T - 1) * n + (size_t)lane;
+    // last row: 1.0 - dones is float64 in numpy, so gamma * last_values rounds to float32 and the
+    // rest of this delta is float64; `+ 0.0` is the recurrence's term of the zero initial L
+    float nv, nnt;
+    double L;
+    {
+        const GaeRow x = gae_load<BOOT>(top, rew, val, es, trunc, tval);
+        const double nnt64 = 1.0 - (last_done[lane] ? 1.0 : 0.0);
+        const float gnv = g32 * last_val[lane];
+        L = (((double)gae_reward<BOOT>(x, g32) + (double)gnv * nnt64) - (double)x.v) + 0.0;
+        const float a = (float)L;
+        adv[top] = a;
+        ret[top] = a + x.v;
+        nv = x.v;
+        nnt = 1.0f - (x.es ? 1.0f : 0.0f);
+    }
+    // rows s, s-1, ..., s-GAE_ROWS+1 per block: element j of a block is row s-j
+    int s = T - 2;
+    size_t i = top - n;   // index of row s (unused when s < 0)
+    if (s >= GAE_ROWS - 1) {
+        GaeRow cur[GAE_ROWS], nxt[GAE_ROWS];
+#pragma unroll
+        for (int j = 0; j < GAE_ROWS; ++j) cur[j] = gae_load<BOOT>(i - (size_t)j * n, rew, val, es, trunc, tval);
+        while (s - GAE_ROWS >= GAE_ROWS - 1) {
+            const size_t i2 = i - (size_t)GAE_ROWS * n;
+#pragma unroll
+            for (int j = 0; j < GAE_ROWS; ++j) nxt[j] = gae_load<BOOT>(i2 - (size_t)j * n, rew, val, es, trunc, tval);
+#pragma unroll
+            for (int j = 0; j < GAE_ROWS; ++j) gae_row<BOOT>(cur[j], i - (size_t)j * n, g32, c32, L, nv, nnt, adv, ret);
+#pragma unroll
+            for (int j = 0; j < GAE_ROWS; ++j) cur[j] = nxt[j];
+            s -= GAE_ROWS;
+            i = i2;
+        }
+#pragma unroll
+        for (int j = 0; j < GAE_ROWS; ++j) gae_row<BOOT>(cur[j], i - (size_t)j * n, g32, c32, L, nv, nnt, adv, ret);
+        s -= GAE_ROWS;
+        i -= (size_t)GAE_ROWS * n;   // wraps when s is now -1; not used then
+    }
+    for (; s >= 0; --s, i -= n) gae_row<BOOT>(gae_load<BOOT>(i, rew, val, es, trunc, tval), i, g32, c32, L, nv, nnt, adv, ret);
+}
+
 thread_local std::string g_norm_create_error;
 
 }  // namespace
@@ -298,6 +395,45 @@ int mrp_norm_set_stats(mrp_norm* n, const double* in) {
     NCHK(n, hipSetDevice(n->device));
     NCHK(n, hipMemcpyAsync(n->d_stats, in, n->n_stats() * sizeof(double), hipMemcpyHostToDevice, n->stream));
     NCHK(n, hipStreamSynchronize(n->stream));
+    return MRP_OK;
+}
+
+int mrp_gae_device(int device, void* hip_stream, int n_steps, int n_lanes, const float* d_rewards, const float* d_values,
+                   const uint8_t* d_episode_starts, const uint8_t* d_truncated, const float* d_terminal_values,
+                   const float* d_last_values, const uint8_t* d_last_dones, double gamma, double gae_lambda,
+                   float* d_advantages, float* d_returns) {
+    std::string& err = g_norm_create_error;
+    err.clear();
+    auto bad = [&](const char* what) { err = std::string("mrp_gae_device: ") + what; return MRP_E_ARG; };
+    // every check that needs no device comes before the first HIP call
+    if (n_steps < 1) return bad("n_steps < 1");
+    if (n_lanes < 1) return bad("n_lanes < 1");
+    if (!d_rewards || !d_values || !d_episode_starts || !d_last_values || !d_last_dones || !d_advantages || !d_returns)
+        return bad("null pointer");
+    if ((d_truncated == nullptr) != (d_terminal_values == nullptr))
+        return bad("d_truncated and d_terminal_values are given together or not at all");
+    const void* ins[] = {d_rewards, d_values, d_episode_starts, d_truncated, d_terminal_values, d_last_values, d_last_dones};
+    for (const void* p : ins)
+        if (p && (p == (const void*)d_advantages || p == (const void*)d_returns)) return bad("an output aliases an input");
+    if (d_advantages == d_returns) return bad("d_advantages and d_returns are the same array");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        err = "no HIP device available (no CPU fallback)";
+        return MRP_E_HIP;
+    }
+    if (device < 0 || device >= ndev) return bad("device index out of range");
+    hipError_t e;
+    if ((e = hipSetDevice(device)) != hipSuccess) { err = std::string("hipSetDevice: ") + hipGetErrorString(e); return MRP_E_HIP; }
+    const float g32 = (float)gamma, c32 = (float)(gamma * gae_lambda);
+    const dim3 grid((unsigned)(((long long)n_lanes + GAE_NT - 1) / GAE_NT)), block(GAE_NT);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (d_truncated)
+        hipLaunchKernelGGL(k_gae<true>, grid, block, 0, st, n_steps, n_lanes, d_rewards, d_values, d_episode_starts, d_truncated,
+                           d_terminal_values, d_last_values, d_last_dones, g32, c32, d_advantages, d_returns);
+    else
+        hipLaunchKernelGGL(k_gae<false>, grid, block, 0, st, n_steps, n_lanes, d_rewards, d_values, d_episode_starts, d_truncated,
+                           d_terminal_values, d_last_values, d_last_dones, g32, c32, d_advantages, d_returns);
+    if ((e = hipGetLastError()) != hipSuccess) { err = std::string("k_gae launch: ") + hipGetErrorString(e); return MRP_E_HIP; }
     return MRP_OK;
 }
 

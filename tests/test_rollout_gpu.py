@@ -1,0 +1,193 @@
+"""The rollout layer on the device: mrp_gae_device (csrc/mrp_norm.hip k_gae) against its numpy rule
+gym_puzzles_amd.rollout.gae_ref (tests/test_rollout.py pins that on the CPU), bit for bit, and the
+DeviceRolloutBuffer around it.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from gym_puzzles_amd.rollout import gae_ref
+
+pytestmark = pytest.mark.gpu
+
+# (1, 1): only the last-row branch; (7, 65): a second, partial wave and fewer rows than one block of the
+# kernel's unrolled walk; (33, 130) and (17, 257): whole blocks (32 and 16 rows below the last);
+# (20, 70): two blocks and then three single rows
+SHAPES = ((1, 1), (2, 3), (7, 65), (33, 130), (17, 257), (20, 70))
+COEFFS = ((0.99, 0.95), (1.0, 1.0), (0.9, 0.0))
+
+
+def _inputs(T, N, seed=0):
+    rs = np.random.RandomState(seed)
+    f32 = np.float32
+    r, v = rs.standard_normal((T, N)).astype(f32), rs.standard_normal((T, N)).astype(f32)
+    es = (rs.uniform(size=(T, N)) < 0.2).astype(np.uint8)
+    lv, dones = rs.standard_normal(N).astype(f32), (rs.uniform(size=N) < 0.2).astype(np.uint8)
+    ends = np.concatenate([es[1:], dones[None]])          # rows whose next row starts an episode
+    trunc = (ends.astype(bool) & (rs.uniform(size=(T, N)) < 0.5)).astype(np.uint8)
+    tv = rs.standard_normal((T, N)).astype(f32)
+    return dict(r=r, v=v, es=es, lv=lv, dones=dones, trunc=trunc, tv=tv)
+
+
+def _ref(x, gamma, lam, boot):
+    return gae_ref(x["r"], x["v"], x["es"].astype(np.float32), x["lv"], x["dones"], gamma, lam,
+                   x["trunc"] if boot else None, x["tv"] if boot else None)
+
+
+def _dev(x):
+    import torch
+    return {k: torch.from_numpy(a).cuda() for k, a in x.items()}
+
+
+def _run(d, gamma, lam, boot, **out):
+    from gym_puzzles_amd.rollout import gae_device
+    return gae_device(d["r"], d["v"], d["es"], d["lv"], d["dones"], gamma, lam, d["trunc"] if boot else None,
+                      d["tv"] if boot else None, **out)
+
+
+def _same(got, want, what):
+    got = got.cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape, what
+    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    assert np.array_equal(got, want) and len(bad) == 0, f"{what}: {len(bad)} elements differ, first at {bad[:1]}"
+
+
+@pytest.mark.parametrize("boot", [False, True], ids=["plain", "bootstrap"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_gae_device_bitwise(gpu_lib, shape, boot):
+    import torch
+    T, N = shape
+    x = _inputs(T, N, seed=T * 1000 + N)
+    if boot and T * N >= 7 * 65:
+        assert x["trunc"].any(), "the case exercises the bootstrap"
+    d = _dev(x)
+    for gamma, lam in COEFFS:
+        want_a, want_r = _ref(x, gamma, lam, boot)
+        adv, ret = _run(d, gamma, lam, boot)
+        _same(adv, want_a, f"advantages {shape} gamma={gamma} lambda={lam}")
+        _same(ret, want_r, f"returns {shape} gamma={gamma} lambda={lam}")
+    # caller-provided outputs: the same tensors come back, with the same bytes
+    A, Rt = torch.full((T, N), -7.0, device="cuda"), torch.full((T, N), -7.0, device="cuda")
+    a2, r2 = _run(d, gamma, lam, boot, advantages=A, returns=Rt)
+    assert a2 is A and r2 is Rt
+    assert torch.equal(A.view(torch.int32), adv.view(torch.int32)) and torch.equal(Rt.view(torch.int32), ret.view(torch.int32))
+    for k, a in x.items():
+        assert np.array_equal(d[k].cpu().numpy(), a), f"input {k} was written"
+
+
+def test_gae_device_lanes_are_independent(gpu_lib):
+    import torch
+    T, N = 17, 257
+    x = _inputs(T, N, seed=11)
+    adv, ret = _run(_dev(x), 0.99, 0.95, True)
+    for lo, hi in ((0, 100), (100, 257)):
+        part = {k: np.ascontiguousarray(a[..., lo:hi]) for k, a in x.items()}
+        a, r = _run(_dev(part), 0.99, 0.95, True)
+        assert torch.equal(a, adv[:, lo:hi]) and torch.equal(r, ret[:, lo:hi])
+
+
+def test_rollout_end_to_end(gpu_lib):
+    """12 steps of 64 lockstep lanes with a 5-step TimeLimit: every lane truncates twice, and the
+    buffer's advantages equal gae_ref on the host copies of its own rows."""
+    import torch
+    from gym_puzzles_amd import DeviceRolloutBuffer, MultiRobotPuzzleVecEnv
+    N, T = 64, 12
+    env = MultiRobotPuzzleVecEnv("MultiRobotPuzzle-v0", N, seed=3, max_episode_steps=5)
+    dev = torch.device("cuda", 0)
+    O, A = env.observation_space.shape[0], env.action_space.shape[0]
+    gen = torch.Generator(device=dev).manual_seed(5)
+    w = torch.linspace(-0.5, 0.5, O, device=dev)
+    V = lambda o: (o * w).sum(-1)  # noqa: E731
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
+    buf = DeviceRolloutBuffer(T, N, (O,), A, device=0, gamma=0.99, gae_lambda=0.95)
+    obs = torch.from_numpy(env.reset()).to(dev)
+    nxt, rew, done, trunc, term = z(N, O), z(N), z(N, dt=torch.uint8), z(N, dt=torch.uint8), z(N, O)
+    start = torch.ones(N, dtype=torch.uint8, device=dev)
+    with pytest.raises(RuntimeError):
+        buf.compute_returns_and_advantage(V(obs), done)
+    for _ in range(T):
+        act = torch.rand(N, A, generator=gen, device=dev) * 2 - 1
+        env.step_torch(act, nxt, rew, done, truncated=trunc, terminal_obs=term)
+        buf.add(obs, act, rew, start, V(obs), z(N), truncated=trunc, terminal_value=V(term))
+        obs, start = nxt.clone(), done.clone()
+    assert buf.full
+    with pytest.raises(RuntimeError):
+        buf.add(obs, act, rew, start, V(obs), z(N))
+    last_values = V(obs)
+    adv, ret = buf.compute_returns_and_advantage(last_values, done)
+    assert adv is buf.advantages and ret is buf.returns
+    h = lambda t: t.cpu().numpy()  # noqa: E731
+    args = (h(buf.rewards), h(buf.values), h(buf.episode_starts).astype(np.float32), h(last_values), h(done), 0.99, 0.95)
+    want_a, want_r = gae_ref(*args, h(buf.truncated), h(buf.terminal_values))
+    _same(adv, want_a, "advantages")
+    _same(ret, want_r, "returns")
+    assert int(h(buf.truncated).sum()) >= 64
+    plain_a, _ = gae_ref(*args)
+    assert not np.array_equal(plain_a, want_a), "the bootstrap is visible in the advantages"
+    assert h(buf.episode_starts)[0].all() and (h(buf.episode_starts)[1:] >= h(buf.truncated)[:-1]).all()
+    env.close()
+
+
+def _filled(T, N, obs_shape, act_dim, obs_dtype, seed):
+    import torch
+    from gym_puzzles_amd import DeviceRolloutBuffer
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    buf = DeviceRolloutBuffer(T, N, obs_shape, act_dim, obs_dtype=obs_dtype)
+    for t in range(T):
+        if obs_dtype == torch.uint8:
+            obs = torch.randint(0, 256, (N,) + tuple(obs_shape), generator=g, device=dev, dtype=torch.uint8)
+        else:
+            obs = torch.randn((N,) + tuple(obs_shape), generator=g, device=dev)
+        rnd = lambda *s: torch.randn(s, generator=g, device=dev)  # noqa: E731
+        # log_probs carry the sample's flat index in swap_and_flatten order: lane * T + row
+        index = (torch.arange(N, device=dev) * T + t).to(torch.float32)
+        buf.add(obs, rnd(N, act_dim), rnd(N), torch.zeros(N, dtype=torch.uint8, device=dev), rnd(N), index)
+    buf.compute_returns_and_advantage(torch.zeros(N, device=dev), torch.zeros(N, dtype=torch.uint8, device=dev))
+    return buf
+
+
+@pytest.mark.parametrize("kind", ["float32", "uint8"])
+def test_rollout_get_minibatches(gpu_lib, kind):
+    import torch
+    T, N = 7, 33                                              # 231 samples: batches of 100, 100, 31
+    obs_shape, dt = ((5,), torch.float32) if kind == "float32" else ((6, 4, 1), torch.uint8)
+    buf = _filled(T, N, obs_shape, 3, dt, seed=2)
+    assert not buf.truncated.any() and not buf.terminal_values.any()
+    g = torch.Generator(device=buf.device).manual_seed(9)
+    batches = list(buf.get(batch_size=100, generator=g))
+    assert [len(b[3]) for b in batches] == [100, 100, 31]
+    seen = torch.cat([b[3] for b in batches]).to(torch.int64)
+    assert torch.equal(torch.sort(seen).values, torch.arange(T * N, device=buf.device))
+    assert not torch.equal(seen, torch.arange(T * N, device=buf.device)), "the order is shuffled"
+    fields = (buf.observations, buf.actions, buf.values, buf.log_probs, buf.advantages, buf.returns)
+    for b in batches:
+        i = b[3].to(torch.int64)
+        row, lane = i % T, i // T
+        assert b[0].dtype == dt and tuple(b[0].shape[1:]) == obs_shape
+        for got, field in zip(b, fields):
+            assert torch.equal(got, field[row, lane])
+    (everything,) = list(buf.get())
+    assert all(len(f) == T * N for f in everything)
+    buf.reset()
+    assert buf.pos == 0 and not buf.full
+
+
+def test_gae_device_argument_errors(gpu_lib):
+    import torch
+    T, N = 4, 6
+    d = _dev(_inputs(T, N))
+    ok = lambda **kw: _run(dict(d, **kw), 0.99, 0.95, True)  # noqa: E731
+    ok()
+    wide = torch.zeros(T, 2 * N, device="cuda")
+    for kw in (dict(r=d["r"].cpu()), dict(v=d["v"].cpu()), dict(v=d["v"].double()), dict(es=d["es"].float()),
+               dict(r=wide[:, ::2]), dict(v=wide[:, :N]), dict(lv=d["lv"][:-1].contiguous()), dict(tv=wide),
+               dict(dones=d["dones"].bool())):
+        with pytest.raises(ValueError):
+            ok(**kw)
+    from gym_puzzles_amd.rollout import gae_device
+    with pytest.raises(ValueError):
+        gae_device(d["r"], d["v"], d["es"], d["lv"], d["dones"], 0.99, 0.95, truncated=d["trunc"])
+    with pytest.raises(ValueError):
+        gae_device(d["r"], d["v"], d["es"], d["lv"], d["dones"], 0.99, 0.95, returns=d["v"])
