@@ -24,18 +24,73 @@ COUNTER_NAMES = ("steps", "resets", "toi_events", "position_iterations", "touchi
 
 MAXF = 24   # csrc/mrp_config.h: fixtures per env (mrp_shapes fills MAXF rows)
 
-# every symbol include/mrp.h declares (tests/test_abi.py checks the .so exports all of them)
-EXPORTED = (
-    "mrp_env_dims", "mrp_create", "mrp_destroy", "mrp_last_error", "mrp_n_lanes", "mrp_env_id",
-    "mrp_set_stream", "mrp_synchronize", "mrp_set_reward_params", "mrp_update_params", "mrp_update_goal",
-    "mrp_reset", "mrp_reset_device", "mrp_step", "mrp_step_device", "mrp_step_ex", "mrp_step_device_ex",
-    "mrp_step_n_device", "mrp_set_auto_reset", "mrp_set_frameskip", "mrp_set_seed", "mrp_set_schedule", "mrp_get_schedule",
-    "mrp_get_bodies", "mrp_get_flags", "mrp_get_faults", "mrp_counters", "mrp_counters_ex", "mrp_state_words", "mrp_get_state", "mrp_set_state",
-    "mrp_set_time_limit", "mrp_selftest_sincos", "mrp_debug_stamps", "mrp_debug_stamps_ext",
-    "mrp_debug_trace", "mrp_debug_trace_words", "mrp_debug_progress", "mrp_debug_velbench", "mrp_debug_posbench", "mrp_norm_create", "mrp_norm_destroy", "mrp_norm_last_error", "mrp_norm_set_stream",
-    "mrp_norm_set_training", "mrp_norm_set_norm_obs", "mrp_norm_reset_device", "mrp_norm_step_device", "mrp_norm_step_device_ex", "mrp_norm_get_stats", "mrp_norm_set_stats",
-    "mrp_gae_device", "mrp_render", "mrp_render_device", "mrp_get_goals", "mrp_shapes", "mrp_pixels", "mrp_pixels_device",
-)
+_i, _d, _u64, _P = ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p
+_ip, _PP = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)
+# The C ABI of include/mrp.h, stated once: name -> (restype, argtypes).  load() applies it, EXPORTED is
+# its key list, and tests/test_abi.py compares that list with the header and with the library's exports.
+# Every build exports the whole ABI (the diagnostics answer MRP_E_STATE outside their -D builds), so an
+# A/B library must be built from this ABI too: a missing symbol raises in load().
+ABI = {
+    "mrp_env_dims": (_i, [_i, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "mrp_create": (_i, [_i, _i, _i, _u64, _u64, _PP]),
+    "mrp_destroy": (None, [_P]),
+    "mrp_last_error": (ctypes.c_char_p, [_P]),
+    "mrp_n_lanes": (_i, [_P]),
+    "mrp_env_id": (_i, [_P]),
+    "mrp_set_stream": (_i, [_P, _P]),
+    "mrp_synchronize": (_i, [_P]),
+    "mrp_set_reward_params": (_i, [_P] + [_d] * 7),
+    "mrp_update_params": (_i, [_P, _d, _d]),
+    "mrp_update_goal": (_i, [_P, _d, _d]),
+    "mrp_reset": (_i, [_P] * 5),
+    "mrp_reset_device": (_i, [_P] * 5),
+    "mrp_step": (_i, [_P] * 8),
+    "mrp_step_device": (_i, [_P] * 8),
+    "mrp_step_ex": (_i, [_P] * 9),
+    "mrp_step_device_ex": (_i, [_P] * 9),
+    "mrp_step_n_device": (_i, [_P, _i] + [_P] * 8),
+    "mrp_set_auto_reset": (_i, [_P, _i]),
+    "mrp_set_frameskip": (_i, [_P, _i]),
+    "mrp_set_seed": (_i, [_P, _u64]),
+    "mrp_set_schedule": (_i, [_P, _i]),
+    "mrp_get_schedule": (_i, [_P]),
+    "mrp_set_time_limit": (_i, [_P, _i]),
+    "mrp_get_bodies": (_i, [_P, _P]),
+    "mrp_get_flags": (_i, [_P, _P]),
+    "mrp_get_faults": (_i, [_P, _P]),
+    "mrp_counters": (_i, [_P, _P, _P]),
+    "mrp_counters_ex": (_i, [_P, _P]),
+    "mrp_state_words": (_i, [_i]),
+    "mrp_get_state": (_i, [_P, _P]),
+    "mrp_set_state": (_i, [_P, _P]),
+    "mrp_get_goals": (_i, [_P, _P]),
+    "mrp_shapes": (_i, [_i, _P, _P, _P, _P]),
+    "mrp_render": (_i, [_P, _P, _i, _i, _i, _P]),
+    "mrp_render_device": (_i, [_P, _P, _i, _i, _i, _P]),
+    "mrp_pixels": (_i, [_P, _i, _i, _i, _i, _P, _P, _P]),
+    "mrp_pixels_device": (_i, [_P, _i, _i, _i, _i, _P, _P, _P]),
+    "mrp_selftest_sincos": (_i, [_i, _P, _P, _P, _i]),
+    "mrp_debug_stamps": (_i, [_i, _P]),
+    "mrp_debug_stamps_ext": (_i, [_i, _P, _P, _P]),
+    "mrp_debug_trace": (_i, [_i, _P, _i]),
+    "mrp_debug_trace_words": (_i, []),
+    "mrp_debug_progress": (_i, [_i, _PP, _i]),
+    "mrp_debug_velbench": (_i, [_i, _i, _i, _i, _i, _P]),
+    "mrp_debug_posbench": (_i, [_i, _i, _i, _i, _i, _P]),
+    "mrp_norm_create": (_i, [_i, _i, _i, _d, _d, _d, _d, _PP]),
+    "mrp_norm_destroy": (None, [_P]),
+    "mrp_norm_last_error": (ctypes.c_char_p, [_P]),
+    "mrp_norm_set_stream": (_i, [_P, _P]),
+    "mrp_norm_set_training": (_i, [_P, _i]),
+    "mrp_norm_set_norm_obs": (_i, [_P, _i]),
+    "mrp_norm_reset_device": (_i, [_P, _P, _P]),
+    "mrp_norm_step_device": (_i, [_P] * 10),
+    "mrp_norm_step_device_ex": (_i, [_P] * 11),
+    "mrp_norm_get_stats": (_i, [_P, _P]),
+    "mrp_norm_set_stats": (_i, [_P, _P]),
+    "mrp_gae_device": (_i, [_i, _P, _i, _i] + [_P] * 7 + [_d, _d, _P, _P]),
+}
+EXPORTED = tuple(ABI)
 
 _lib = None
 
@@ -53,72 +108,9 @@ def load(path: str | None = None) -> ctypes.CDLL:
     if not os.path.exists(LIB_PATH_):
         raise MrpError(f"{LIB_PATH} not built; run `python -m gym_puzzles_amd.build` (hipcc, gfx950)")
     L = ctypes.CDLL(LIB_PATH_)
-    i, d, u64, P = ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p
-    ip = ctypes.POINTER(ctypes.c_int)
-    L.mrp_env_dims.argtypes = [i, ip, ip, ip, ip, ip, ip]
-    L.mrp_create.argtypes = [i, i, i, u64, u64, ctypes.POINTER(P)]
-    L.mrp_destroy.argtypes = [P]
-    L.mrp_destroy.restype = None
-    L.mrp_last_error.argtypes = [P]
-    L.mrp_last_error.restype = ctypes.c_char_p
-    L.mrp_n_lanes.argtypes = [P]
-    L.mrp_env_id.argtypes = [P]
-    L.mrp_set_stream.argtypes = [P, P]
-    L.mrp_synchronize.argtypes = [P]
-    L.mrp_set_reward_params.argtypes = [P, d, d, d, d, d, d, d]
-    L.mrp_update_params.argtypes = [P, d, d]
-    L.mrp_update_goal.argtypes = [P, d, d]
-    L.mrp_reset.argtypes = [P, P, P, P, P]
-    L.mrp_reset_device.argtypes = [P, P, P, P, P]
-    L.mrp_step.argtypes = [P, P, P, P, P, P, P, P]
-    L.mrp_step_device.argtypes = [P, P, P, P, P, P, P, P]
-    L.mrp_step_ex.argtypes = [P, P, P, P, P, P, P, P, P]
-    L.mrp_step_device_ex.argtypes = [P, P, P, P, P, P, P, P, P]
-    L.mrp_step_n_device.argtypes = [P, i, P, P, P, P, P, P, P, P]
-    L.mrp_set_seed.argtypes = [P, u64]
-    L.mrp_set_schedule.argtypes = [P, i]
-    L.mrp_get_schedule.argtypes = [P]
-    L.mrp_set_auto_reset.argtypes = [P, i]
-    L.mrp_set_frameskip.argtypes = [P, i]
-    L.mrp_get_bodies.argtypes = [P, P]
-    L.mrp_get_flags.argtypes = [P, P]
-    L.mrp_get_faults.argtypes = [P, P]
-    L.mrp_counters.argtypes = [P, P, P]
-    L.mrp_counters_ex.argtypes = [P, P]
-    L.mrp_state_words.argtypes = [i]
-    L.mrp_get_state.argtypes = [P, P]
-    L.mrp_set_state.argtypes = [P, P]
-    L.mrp_set_time_limit.argtypes = [P, i]
-    L.mrp_selftest_sincos.argtypes = [i, P, P, P, i]
-    L.mrp_render.argtypes = [P, P, i, i, i, P]
-    L.mrp_render_device.argtypes = [P, P, i, i, i, P]
-    L.mrp_pixels.argtypes = [P, i, i, i, i, P, P, P]
-    L.mrp_pixels_device.argtypes = [P, i, i, i, i, P, P, P]
-    L.mrp_get_goals.argtypes = [P, P]
-    L.mrp_shapes.argtypes = [i, P, P, P, P]
-    L.mrp_debug_stamps.argtypes = [i, P]
-    L.mrp_norm_create.argtypes = [i, i, i, d, d, d, d, ctypes.POINTER(P)]
-    L.mrp_norm_destroy.argtypes = [P]
-    L.mrp_norm_destroy.restype = None
-    L.mrp_norm_last_error.argtypes = [P]
-    L.mrp_norm_last_error.restype = ctypes.c_char_p
-    L.mrp_norm_set_stream.argtypes = [P, P]
-    L.mrp_norm_set_training.argtypes = [P, i]
-    L.mrp_norm_set_norm_obs.argtypes = [P, i]
-    L.mrp_norm_reset_device.argtypes = [P, P, P]
-    L.mrp_norm_step_device.argtypes = [P] * 10
-    L.mrp_norm_step_device_ex.argtypes = [P] * 11
-    L.mrp_norm_get_stats.argtypes = [P, P]
-    L.mrp_norm_set_stats.argtypes = [P, P]
-    L.mrp_gae_device.argtypes = [i, P, i, i, P, P, P, P, P, P, P, d, d, P, P]
-    # every build exports the whole ABI of include/mrp.h (the diagnostics answer MRP_E_STATE outside
-    # their -D builds), so an A/B library must be built from this ABI too: a missing symbol raises here
-    L.mrp_debug_stamps_ext.argtypes = [i, P, P, P]
-    L.mrp_debug_trace.argtypes = [i, P, i]
-    L.mrp_debug_trace_words.argtypes = []
-    L.mrp_debug_progress.argtypes = [i, ctypes.POINTER(P), i]
-    L.mrp_debug_velbench.argtypes = [i, i, i, i, i, P]
-    L.mrp_debug_posbench.argtypes = [i, i, i, i, i, P]
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

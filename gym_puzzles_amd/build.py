@@ -25,7 +25,7 @@ with open(os.path.join(CSRC, "mrp_config.h")) as _f:   # the rows of MRP_ENV_LIS
 SOURCES = ([(f, f + ".o", None) for f in ("mrp_kernels.hip", "mrp_tables.cpp", "mrp_norm.hip")]
            + [("mrp_unit.hip", f"mrp_env{e}.o", e) for e in range(N_ENVS)])
 HEADERS = ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h", "mrp_ops.h", "mrp_lane.h", "mrp_render.h",
-           "mrp_pixels.h")
+           "mrp_pixels.h", "mrp_microbench.h")
 
 
 def deps(csrc: str = CSRC) -> list[str]:

@@ -42,7 +42,7 @@ template <int ENV> struct Env : World<ENV> {
         for (int i = 0; i < TN; ++i) { S.tpar[i] = i + 1 < TN ? i + 1 : NULLN; S.th[i] = -1; S.tud[i] = -1; S.tc1[i] = NULLN; S.tc2[i] = NULLN; }
         S.root = NULLN; S.freeList = 0; S.nodeCount = 0; S.moveCount = 0;
         S.cHead = NULLN; S.cFree = 0; S.cCount = 0; S.cHW = 0;
-        for (int c = 0; c < D::CMAX; ++c) S.cnext[c] = c + 1 < D::CMAX ? c + 1 : NULLN;
+        for (int c = 0; c < D::CMAX; ++c) S.cnext[c] = (int)contact_slot_init(c, D::CMAX);
         S.inv_dt0 = 0.0f; S.newFixture = 0; S.haveBodies = 0; S.episode = 0; S.stepCounter = 0;
         S.elapsed = 0; S.blks_in_place = 0; S.prev_blks_in_place = 0; S.wall_contact = 0;
         S.toiEvents = 0; S.posIters = 0; S.touching = 0; S.nonfinite = 0;
@@ -54,7 +54,7 @@ template <int ENV> struct Env : World<ENV> {
     __device__ __forceinline__ void destroy_bodies() {
         if (!S.haveBodies) return;
         S.cHead = NULLN; S.cFree = 0; S.cCount = 0;
-        for (int c = 0; c < D::CMAX; ++c) S.cnext[c] = c + 1 < D::CMAX ? c + 1 : NULLN;
+        for (int c = 0; c < D::CMAX; ++c) S.cnext[c] = (int)contact_slot_init(c, D::CMAX);
         if (D::V == 3) {
             for (int b = ND; b < ND + 4; ++b) for (int k = T.body_nfix[b] - 1; k >= 0; --k) this->destroy_proxy(T.body_fix0[b] + k);
             for (int b = 0; b < ND; ++b) for (int k = T.body_nfix[b] - 1; k >= 0; --k) this->destroy_proxy(T.body_fix0[b] + k);

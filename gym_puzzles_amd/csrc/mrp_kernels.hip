@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -72,7 +73,26 @@ __global__ __launch_bounds__(256) void k_iota(int* __restrict__ order, int nl) {
 // ------------------------------------------------------------------------------ host side
 thread_local std::string g_create_error;
 
+// A temporary buffer of one call, freed when the call returns: device memory, or with PINNED
+// device-mapped host memory.
+template <class T, bool PINNED = false>
+class Scoped {
+    T* p_ = nullptr;
 
+public:
+    Scoped() = default;
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+    ~Scoped() {
+        if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+    }
+    hipError_t alloc(size_t bytes) {
+        if (p_) return hipErrorInvalidValue;   // one buffer per owner: a second one would leak the first
+        return PINNED ? hipHostMalloc((void**)&p_, bytes, hipHostMallocMapped) : hipMalloc((void**)&p_, bytes);
+    }
+    T* get() const { return p_; }
+    T* release() { T* p = p_; p_ = nullptr; return p; }   // mrp_debug_progress hands its buffer to the caller
+};
 }  // namespace
 
 struct mrp_ctx {
@@ -114,6 +134,18 @@ struct mrp_ctx {
     int32_t* d_flags = nullptr;
     int64_t* d_ctr = nullptr;    // [CTR_N] mrp_counters_ex
     std::string err;
+    // every device buffer the context owns: mrp_create allocates from this table, mrp_destroy frees from it
+    struct DevBuf { void** p; size_t bytes; };
+    std::array<DevBuf, 7> device_buffers() {
+        const size_t nl = (size_t)n_lanes;
+        return {{{(void**)&d_state, (size_t)words * nl * 4},
+                 {(void**)&d_bodies, nl * 6 * (n_agents + n_blocks) * sizeof(float)},
+                 {(void**)&d_flags, nl * (n_agents + 1) * sizeof(int32_t)},
+                 {(void**)&d_ctr, CTR_N * sizeof(int64_t)},
+                 {(void**)&d_order, nl * sizeof(int)},
+                 {(void**)&d_cost, nl * sizeof(uint32_t)},
+                 {(void**)&d_costmax, sizeof(uint32_t)}}};
+    }
 };
 
 #define HIPCHK(ctx, expr)                                                   \
@@ -162,13 +194,9 @@ void mrp_destroy(mrp_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    void* bufs[] = {ctx->d_state, ctx->d_bodies, ctx->d_flags, ctx->d_ctr};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    for (auto& b : ctx->device_buffers())
+        if (*b.p) (void)hipFree(*b.p);
     if (ctx->h_io) (void)hipHostFree(ctx->h_io);
-    if (ctx->d_order) (void)hipFree(ctx->d_order);
-    if (ctx->d_cost) (void)hipFree(ctx->d_cost);
-    if (ctx->d_costmax) (void)hipFree(ctx->d_costmax);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -225,21 +253,20 @@ int mrp_create(int env_id, int n_lanes, int device, uint64_t seed, uint64_t lane
     if ((e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
     ctx->stream = ctx->own_stream;
     size_t nl = (size_t)n_lanes;
-    struct { void** p; size_t bytes; } allocs[] = {
-        {(void**)&ctx->d_state, (size_t)ctx->words * nl * 4},
-        {(void**)&ctx->d_bodies, nl * 6 * (ctx->n_agents + ctx->n_blocks) * sizeof(float)},
-        {(void**)&ctx->d_flags, nl * (ctx->n_agents + 1) * sizeof(int32_t)},
-        {(void**)&ctx->d_ctr, CTR_N * sizeof(int64_t)},
-    };
     // MRP_STATE_ALLOC=contiguous (diagnostic A/B): the lane state as one physically contiguous
     // allocation (large page fragments, so the GPU TLB covers it with few entries)
     const char* pol = std::getenv("MRP_STATE_ALLOC");
     const bool contiguous = pol && std::strcmp(pol, "contiguous") == 0;
-    for (auto& a : allocs) {
-        if (contiguous && a.p == (void**)&ctx->d_state) e = hipExtMallocWithFlags(a.p, a.bytes, hipDeviceMallocContiguous);
-        else e = hipMalloc(a.p, a.bytes);
-        if (e != hipSuccess) return fail("hipMalloc", e);
-    }
+    // The table's buffers in the order the timings were taken with: the first four, the pinned I/O
+    // buffer, then the scheduling buffers (the allocator's addresses, the caller's later buffers
+    // included, follow from the order).
+    const auto bufs = ctx->device_buffers();
+    auto alloc = [&](const mrp_ctx::DevBuf& a) {
+        return contiguous && a.p == (void**)&ctx->d_state ? hipExtMallocWithFlags(a.p, a.bytes, hipDeviceMallocContiguous)
+                                                          : hipMalloc(a.p, a.bytes);
+    };
+    for (size_t k = 0; k < 4; ++k)
+        if ((e = alloc(bufs[k])) != hipSuccess) return fail("hipMalloc", e);
     {   // the host API's pinned I/O buffer, carved 16-B aligned: doubles first, then floats, then bytes
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         const size_t sz_draws = up(nl * ctx->n_draws * sizeof(double)), sz_r64 = up(nl * sizeof(double));
@@ -262,9 +289,8 @@ int mrp_create(int env_id, int n_lanes, int device, uint64_t seed, uint64_t lane
         ctx->h_trunc = q; q += sz_b;
         ctx->h_status = q;
     }
-    if ((e = hipMalloc((void**)&ctx->d_order, nl * sizeof(int))) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&ctx->d_cost, nl * sizeof(uint32_t))) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&ctx->d_costmax, sizeof(uint32_t))) != hipSuccess) return fail("hipMalloc", e);
+    for (size_t k = 4; k < bufs.size(); ++k)
+        if ((e = alloc(bufs[k])) != hipSuccess) return fail("hipMalloc", e);
     if ((e = hipMemset(ctx->d_cost, 0, nl * sizeof(uint32_t))) != hipSuccess) return fail("hipMemset", e);
     if ((e = hipMemset(ctx->d_costmax, 0xff, sizeof(uint32_t))) != hipSuccess) return fail("hipMemset", e);
     hipLaunchKernelGGL(k_iota, dim3((n_lanes + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_order, n_lanes);
@@ -495,27 +521,10 @@ int mrp_set_state(mrp_ctx* ctx, const uint32_t* in) {
     if (!ctx || !in) return MRP_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nl = (size_t)ctx->n_lanes, nw = (size_t)ctx->words;
-    // k_step moves only the contact slots below a lane's high-water mark cHW and rebuilds the rest
-    // in LDS with their initial contents (mrp_lane.h StateIO), so a state whose cHW understates its
-    // highest non-initial slot would lose contacts silently.  Recompute the mark from the slots:
-    // 1 + the highest slot whose words differ from the initial ones (cnext[c] = c + 1 or NULL, every
-    // other array 0), never lower than the stored value (a higher mark only moves more words).
-    const EnvOps* o = env_ops(ctx->env_id);
+    // k_step moves only the contact slots below a lane's high-water mark cHW, so an understated mark
+    // is raised to cover the lane's non-initial slots before the upload (StateIO::repair_marks)
     std::vector<uint32_t> st(in, in + nl * nw);
-    const size_t C = (size_t)o->cslot_n;
-    for (size_t l = 0; l < nl; ++l) {
-        uint32_t* w = st.data() + l * nw;
-        int hw = 0;
-        for (size_t a = 0; a < (size_t)o->cslot_arrays; ++a)
-            for (size_t c = (size_t)hw; c < C; ++c) {
-                const uint32_t init = a == 0 ? (c + 1 < C ? (uint32_t)(c + 1) : 0xffffffffu) : 0u;
-                if (w[o->cslot_word + a * C + c] != init) hw = (int)c + 1;
-            }
-        int32_t mark;
-        std::memcpy(&mark, &w[o->chw_word], 4);
-        mark = std::max(std::min(mark, (int32_t)C), (int32_t)hw);
-        std::memcpy(&w[o->chw_word], &mark, 4);
-    }
+    env_ops(ctx->env_id)->repair_marks(st.data(), nl);
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, st.data(), nl * nw * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_reset = 1;
@@ -523,22 +532,11 @@ int mrp_set_state(mrp_ctx* ctx, const uint32_t* in) {
 }
 
 int mrp_counters(mrp_ctx* ctx, int64_t* toi_events, int64_t* pos_iters) {
-    if (!ctx) return MRP_E_ARG;
-    size_t nl = (size_t)ctx->n_lanes, nw = (size_t)ctx->words;
-    std::vector<uint32_t> st(nl * nw);
-    int rc = mrp_get_state(ctx, st.data());
+    int64_t c[CTR_N];
+    const int rc = mrp_counters_ex(ctx, c);
     if (rc) return rc;
-    size_t off = 0;
-    off = (size_t)env_ops(ctx->env_id)->counters_word;
-    int64_t toi = 0, pos = 0;
-    for (size_t l = 0; l < nl; ++l) {
-        int64_t a, b;
-        std::memcpy(&a, &st[l * nw + off], 8);
-        std::memcpy(&b, &st[l * nw + off + 2], 8);
-        toi += a; pos += b;
-    }
-    if (toi_events) *toi_events = toi;
-    if (pos_iters) *pos_iters = pos;
+    if (toi_events) *toi_events = c[CTR_TOI];
+    if (pos_iters) *pos_iters = c[CTR_POS_ITERS];
     return MRP_OK;
 }
 
@@ -556,14 +554,16 @@ int mrp_counters_ex(mrp_ctx* ctx, int64_t* out8) {
 int mrp_debug_progress(int device, uint32_t** host_words, int n_lanes) {
     if (!host_words || n_lanes <= 0 || hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
     if (env_ops(0)->debug_progress(nullptr) == hipErrorNotSupported) return MRP_E_STATE;   // not a -DMRP_PROGRESS build
-    uint32_t* h = nullptr;
-    if (hipHostMalloc((void**)&h, (size_t)n_lanes * 4, hipHostMallocMapped) != hipSuccess) return MRP_E_HIP;
-    for (int i = 0; i < n_lanes; ++i) h[i] = 0u;
+    Scoped<uint32_t, true> h;
+    if (h.alloc((size_t)n_lanes * 4) != hipSuccess) return MRP_E_HIP;
+    for (int i = 0; i < n_lanes; ++i) h.get()[i] = 0u;
     uint32_t* d = nullptr;
-    if (hipHostGetDevicePointer((void**)&d, h, 0) != hipSuccess) return MRP_E_HIP;
+    if (hipHostGetDevicePointer((void**)&d, h.get(), 0) != hipSuccess) return MRP_E_HIP;
+    // from here on a unit may hold the address, so the words live as long as the process
+    uint32_t* words = h.release();
     for (int i = 0; i < N_ENVS; ++i)
         if (env_ops(i)->debug_progress(d) != hipSuccess) return MRP_E_HIP;
-    *host_words = h;
+    *host_words = words;
     return MRP_OK;
 }
 
@@ -572,12 +572,11 @@ int mrp_debug_velbench(int device, int nc, int pcount, int iters, int blocks, ui
     if (ncc < 1 || ncc > 6 || pcount < 1 || pcount > 2 || blocks < 1 || !cycles || hipSetDevice(device) != hipSuccess) return MRP_E_ARG;
     EnvTables v0;
     build_tables(0, v0);
-    unsigned long long* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)blocks * 8) != hipSuccess) return MRP_E_HIP;
-    hipError_t e = velbench_launch(v0, nc, pcount, iters, blocks, d);
+    Scoped<unsigned long long> d;
+    if (d.alloc((size_t)blocks * 8) != hipSuccess) return MRP_E_HIP;
+    hipError_t e = velbench_launch(v0, nc, pcount, iters, blocks, d.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(cycles, d, (size_t)blocks * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = hipMemcpy(cycles, d.get(), (size_t)blocks * 8, hipMemcpyDeviceToHost);
     return e == hipSuccess ? MRP_OK : MRP_E_HIP;
 }
 
@@ -586,12 +585,11 @@ int mrp_debug_posbench(int device, int nc, int pcount, int iters, int blocks, ui
         return MRP_E_ARG;
     EnvTables v0;
     build_tables(0, v0);
-    unsigned long long* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)blocks * 16) != hipSuccess) return MRP_E_HIP;
-    hipError_t e = posbench_launch(v0, nc, pcount, iters, blocks, d);
+    Scoped<unsigned long long> d;
+    if (d.alloc((size_t)blocks * 16) != hipSuccess) return MRP_E_HIP;
+    hipError_t e = posbench_launch(v0, nc, pcount, iters, blocks, d.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)blocks * 16, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = hipMemcpy(out, d.get(), (size_t)blocks * 16, hipMemcpyDeviceToHost);
     return e == hipSuccess ? MRP_OK : MRP_E_HIP;
 }
 
@@ -678,22 +676,18 @@ int mrp_render(mrp_ctx* ctx, const int32_t* lanes, int n, int width, int height,
     for (int i = 0; i < n; ++i)
         if (lanes[i] < 0 || lanes[i] >= ctx->n_lanes) { ctx->err = "mrp_render: lane index out of range"; return MRP_E_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int32_t* dl = nullptr; uint8_t* dimg = nullptr;
+    Scoped<int32_t> dl;
+    Scoped<uint8_t> dimg;
     const size_t img = (size_t)n * width * height * 3;
     int rc = MRP_E_HIP;
-    if (hipMalloc(&dl, n * sizeof(int32_t)) == hipSuccess && hipMalloc(&dimg, img) == hipSuccess &&
-        hipMemcpyAsync(dl, lanes, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess) {
-        rc = mrp_render_device(ctx, dl, n, width, height, dimg);
-        if (rc == MRP_OK) {
+    if (dl.alloc(n * sizeof(int32_t)) == hipSuccess && dimg.alloc(img) == hipSuccess &&
+        hipMemcpyAsync(dl.get(), lanes, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess) {
+        rc = mrp_render_device(ctx, dl.get(), n, width, height, dimg.get());
+        if (rc == MRP_OK && !(hipMemcpyAsync(rgb, dimg.get(), img, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                              hipStreamSynchronize(ctx->stream) == hipSuccess))
             rc = MRP_E_HIP;
-            if (hipMemcpyAsync(rgb, dimg, img, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                hipStreamSynchronize(ctx->stream) == hipSuccess)
-                rc = MRP_OK;
-        }
     }
     if (rc == MRP_E_HIP && ctx->err.empty()) ctx->err = "mrp_render: HIP allocation/copy failed";
-    if (dl) (void)hipFree(dl);
-    if (dimg) (void)hipFree(dimg);
     return rc;
 }
 
@@ -732,40 +726,35 @@ int mrp_pixels(mrp_ctx* ctx, int width, int height, int channels, int depth, con
     if (rc != MRP_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nl = (size_t)ctx->n_lanes, bytes = nl * depth * width * height * channels;
-    uint8_t *dd = nullptr, *dp = nullptr, *dn = nullptr;
+    Scoped<uint8_t> dd, dp, dn;   // dd / dp stay null where the caller passes no done bytes / no earlier stack
     rc = MRP_E_HIP;
-    bool ok = hipMalloc(&dn, bytes) == hipSuccess;
+    bool ok = dn.alloc(bytes) == hipSuccess;
     if (ok && done)
-        ok = hipMalloc(&dd, nl) == hipSuccess && hipMemcpyAsync(dd, done, nl, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+        ok = dd.alloc(nl) == hipSuccess && hipMemcpyAsync(dd.get(), done, nl, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     if (ok && prev && depth > 1)
-        ok = hipMalloc(&dp, bytes) == hipSuccess && hipMemcpyAsync(dp, prev, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+        ok = dp.alloc(bytes) == hipSuccess && hipMemcpyAsync(dp.get(), prev, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
     if (ok) {
-        rc = mrp_pixels_device(ctx, width, height, channels, depth, dd, dp, dn);
-        if (rc == MRP_OK) {
+        rc = mrp_pixels_device(ctx, width, height, channels, depth, dd.get(), dp.get(), dn.get());
+        if (rc == MRP_OK && !(hipMemcpyAsync(next, dn.get(), bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                              hipStreamSynchronize(ctx->stream) == hipSuccess))
             rc = MRP_E_HIP;
-            if (hipMemcpyAsync(next, dn, bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                hipStreamSynchronize(ctx->stream) == hipSuccess)
-                rc = MRP_OK;
-        }
     }
     if (rc == MRP_E_HIP && ctx->err.empty()) ctx->err = "mrp_pixels: HIP allocation/copy failed";
-    if (dd) (void)hipFree(dd);
-    if (dp) (void)hipFree(dp);
-    if (dn) (void)hipFree(dn);
     return rc;
 }
 
 int mrp_get_goals(mrp_ctx* ctx, double* out) {
     if (!ctx || !out) return MRP_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    double* d = nullptr;
+    Scoped<double> d;
     const size_t bytes = (size_t)ctx->n_lanes * ctx->n_blocks * 3 * sizeof(double);
-    HIPCHK(ctx, hipMalloc(&d, bytes));
-    env_ops(ctx->env_id)->goals(ctx->stream, ctx->d_state, ctx->n_lanes, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e = d.alloc(bytes);
+    // the text callers have matched on since this was HIPCHK(ctx, hipMalloc(&d, bytes)); kept byte for byte
+    if (e != hipSuccess) { ctx->err = std::string("hipMalloc(&d, bytes): ") + hipGetErrorString(e); return MRP_E_HIP; }
+    env_ops(ctx->env_id)->goals(ctx->stream, ctx->d_state, ctx->n_lanes, d.get());
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d.get(), bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { ctx->err = std::string("mrp_get_goals: ") + hipGetErrorString(e); return MRP_E_HIP; }
     return MRP_OK;
 }
@@ -789,19 +778,16 @@ int mrp_shapes(int env_id, int32_t* n_fix, int32_t* fix_body, int32_t* counts, f
 int mrp_selftest_sincos(int device, const float* x, float* sin_out, float* cos_out, int n) {
     if (!x || !sin_out || !cos_out || n <= 0) return MRP_E_ARG;
     if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
-    float *dx = nullptr, *ds = nullptr, *dc = nullptr;
+    Scoped<float> dx, ds, dc;
     size_t bytes = (size_t)n * sizeof(float);
     int rc = MRP_E_HIP;
-    if (hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&ds, bytes) == hipSuccess && hipMalloc(&dc, bytes) == hipSuccess &&
-        hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_sincos, dim3((n + 255) / 256), dim3(256), 0, 0, dx, ds, dc, n);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(sin_out, ds, bytes, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(cos_out, dc, bytes, hipMemcpyDeviceToHost) == hipSuccess)
+    if (dx.alloc(bytes) == hipSuccess && ds.alloc(bytes) == hipSuccess && dc.alloc(bytes) == hipSuccess &&
+        hipMemcpy(dx.get(), x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_sincos, dim3((n + 255) / 256), dim3(256), 0, 0, dx.get(), ds.get(), dc.get(), n);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(sin_out, ds.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(cos_out, dc.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess)
             rc = MRP_OK;
     }
-    if (dx) (void)hipFree(dx);
-    if (ds) (void)hipFree(ds);
-    if (dc) (void)hipFree(dc);
     return rc;
 }
 

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstring>
 #include <type_traits>
@@ -38,12 +39,12 @@ namespace {
 // LaneState is copied word-by-word; a may_alias word type keeps type-based alias analysis
 // from reordering these copies against the typed (float/int) accesses of the step code.
 typedef uint32_t __attribute__((__may_alias__)) word_t;
+typedef uint4 __attribute__((__may_alias__)) quad_t;
 
 template <int ENV>
 __device__ __forceinline__ void load_state(LaneState<ENV>& S, const uint32_t* __restrict__ g, int lane, int tid) {
     static_assert(sizeof(LaneState<ENV>) % 16 == 0, "lane state moves in 16-B granules");
     constexpr int NQ = (int)(sizeof(LaneState<ENV>) / 16);
-    typedef uint4 __attribute__((__may_alias__)) quad_t;
     quad_t* w = reinterpret_cast<quad_t*>(&S);
     const quad_t* src = reinterpret_cast<const quad_t*>(g + (size_t)lane * lane_words<ENV>());
     for (int i = tid; i < NQ; i += BLOCK) w[i] = src[i];
@@ -51,31 +52,11 @@ __device__ __forceinline__ void load_state(LaneState<ENV>& S, const uint32_t* __
 template <int ENV>
 __device__ __forceinline__ void store_state(const LaneState<ENV>& S, uint32_t* __restrict__ g, int lane, int tid) {
     constexpr int NQ = (int)(sizeof(LaneState<ENV>) / 16);
-    typedef uint4 __attribute__((__may_alias__)) quad_t;
     const quad_t* w = reinterpret_cast<const quad_t*>(&S);
     quad_t* dst = reinterpret_cast<quad_t*>(g + (size_t)lane * lane_words<ENV>());
     for (int i = tid; i < NQ; i += BLOCK) dst[i] = w[i];
 }
 
-// words [A, B) of a lane's state, 16-B granules where aligned (A, B compile-time)
-template <int A, int B, bool LOAD>
-__device__ __forceinline__ void move_words(word_t* lds, word_t* g, int tid) {
-    constexpr int QA = (A + 3) / 4, QB = B / 4;
-    typedef uint4 __attribute__((__may_alias__)) quad_t;
-    if (QA < QB) {
-        for (int i = QA + tid; i < QB; i += BLOCK) {
-            if (LOAD) reinterpret_cast<quad_t*>(lds)[i] = reinterpret_cast<const quad_t*>(g)[i];
-            else reinterpret_cast<quad_t*>(g)[i] = reinterpret_cast<const quad_t*>(lds)[i];
-        }
-        constexpr int H = 4 * QA - A, T = B - 4 * QB;   // head / tail words outside the granules
-        if (tid < H + T) {
-            const int k = tid < H ? A + tid : 4 * QB + (tid - H);
-            if (LOAD) lds[k] = g[k]; else g[k] = lds[k];
-        }
-    } else {
-        for (int k = A + tid; k < B; k += BLOCK) { if (LOAD) lds[k] = g[k]; else g[k] = lds[k]; }
-    }
-}
 // k_step's state round trip: everything but the contact slots >= cHW, which hold their initial
 // contents in HBM and are rebuilt in LDS (LaneState::cHW).  `hw` = the slots to move (load: the
 // stored cHW; store: max(cHW at load, cHW now), so slots a reset in this launch zeroed are
@@ -84,8 +65,8 @@ __device__ __forceinline__ void move_words(word_t* lds, word_t* g, int tid) {
 // The load issues every global load of a region before its first wait (split issue / put), so a
 // lane's state arrives in two memory round trips (the contact mark, then the live contact slots)
 // instead of one per loop trip (~25 before) (round 4 A/B, profiles/r4_ab_batched_load_schedule.txt
-// and r4_ab_contact_words.txt: v2 +2.9 %, the other configs +0-0.6 %).
-typedef uint4 __attribute__((__may_alias__)) quad_t;
+// and r4_ab_contact_words.txt: v2 +2.9 %, the other configs +0-0.6 %).  The store has nothing to
+// wait for and stays a loop.
 // words [A, B) of a lane's state: 16-B granules where aligned, single words at the ragged ends
 template <int A, int B>
 struct Span {
@@ -124,6 +105,14 @@ struct Span {
         for (int k = 0; k < NS; ++k)
             if (has_single(tid, k)) lds[single(tid, k)] = s[k];
     }
+    __device__ __forceinline__ static void store(const word_t* lds, word_t* g, int tid) {
+        if constexpr (QUADS) {
+            for (int i = QA + tid; i < QB; i += BLOCK) reinterpret_cast<quad_t*>(g)[i] = reinterpret_cast<const quad_t*>(lds)[i];
+            if (tid < H + T) g[single(tid, 0)] = lds[single(tid, 0)];
+        } else {
+            for (int k = A + tid; k < B; k += BLOCK) g[k] = lds[k];
+        }
+    }
 };
 template <int ENV>
 struct StateIO {
@@ -142,10 +131,7 @@ struct StateIO {
         static constexpr int NWC = LS::NCA * C, NK = (NWC + BLOCK - 1) / BLOCK;
         word_t w[NK];
         __device__ __forceinline__ static bool live(int i, int hw) { return i % C < hw; }   // i: word of the region
-        __device__ __forceinline__ static word_t init(int i) {
-            // cnext (array 0) chains the free list 0 -> 1 -> ... -> C-1; the other arrays are 0
-            return i < C ? (i + 1 < C ? (word_t)(i + 1) : (word_t)NULLN) : 0u;
-        }
+        __device__ __forceinline__ static word_t init(int i) { return contact_slot_init(i, C); }
         __device__ __forceinline__ void issue(const word_t* g, int hw, int tid) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
@@ -179,10 +165,7 @@ struct StateIO {
         quad_t q[NQ];
         word_t s;
         __device__ __forceinline__ static bool live(int w, int hw) { return (w - P) % C < hw; }
-        __device__ __forceinline__ static word_t init(int w) {
-            const int i = w - P;   // cnext (array 0) chains the free list 0 -> 1 -> ... -> C-1; the rest are 0
-            return i < C ? (i + 1 < C ? (word_t)(i + 1) : (word_t)NULLN) : 0u;
-        }
+        __device__ __forceinline__ static word_t init(int w) { return contact_slot_init(w - P, C); }   // w: word of the lane
         // granule j's first slot; its words are slots c0 .. c0 + 3, wrapping into the next array's
         // slots 0, 1, 2 (C >= 4), so it is live iff c0 < hw or it wraps and slot 0 is live
         __device__ __forceinline__ static int slot0(int j) { return (4 * j - P) % C; }
@@ -225,12 +208,6 @@ struct StateIO {
             if ((tid < H + T) & live(single(tid), hw)) g[single(tid)] = lds[single(tid)];
         }
     };
-#ifndef MRP_CONTACT_GRANULES
-#define MRP_CONTACT_GRANULES 0
-#endif
-#ifndef MRP_FRESH_REGS
-#define MRP_FRESH_REGS 0
-#endif
     using Contacts = typename std::conditional<MRP_CONTACT_GRANULES != 0, ContactGranules, ContactWords>::type;
     // hw_io <- the loaded cHW (clamped to the pool; kept in LDS, not live in registers across the step)
     __device__ __forceinline__ static void load(LS& S, int& hw_io, const uint32_t* __restrict__ gs, int lane, int tid) {
@@ -259,9 +236,26 @@ struct StateIO {
         word_t* g = gs + (size_t)lane * NW;
         word_t* lds = const_cast<word_t*>(reinterpret_cast<const word_t*>(&S));
         const int hw = max(hw_io, min(max(S.cHW, 0), C));
-        move_words<0, P, false>(lds, g, tid);
-        move_words<Q, NW, false>(lds, g, tid);
+        Span<0, P>::store(lds, g, tid);
+        Span<Q, NW>::store(lds, g, tid);
         Contacts::store(lds, g, hw, tid);
+    }
+    // Host side (mrp_set_state): a state whose cHW understates its highest non-initial slot would lose
+    // contacts silently in load() above.  Recompute every lane's mark from its slots: 1 + the highest
+    // slot holding a word that differs from contact_slot_init, never lower than the stored value
+    // clamped to the pool (a higher mark only moves more words).
+    static void repair_marks(uint32_t* state, size_t n_lanes) {
+        for (size_t l = 0; l < n_lanes; ++l) {
+            uint32_t* w = state + l * NW;
+            int hw = 0;
+            for (int a = 0; a < LS::NCA; ++a)
+                for (int c = hw; c < C; ++c)
+                    if (w[P + a * C + c] != contact_slot_init(a * C + c, C)) hw = c + 1;
+            int32_t mark;
+            std::memcpy(&mark, &w[HWW], 4);
+            mark = std::max(std::min(mark, (int32_t)C), (int32_t)hw);
+            std::memcpy(&w[HWW], &mark, 4);
+        }
     }
 };
 
@@ -342,13 +336,6 @@ __global__ __launch_bounds__(BLOCK, 4) void k_reset(uint32_t* state, int nl, con
 }
 
 template <int ENV, bool MULTI>
-#ifndef MRP_STEP_WAVES_PER_EU
-// 3 waves per SIMD (168 VGPRs): k_step without VGPR spills in the solver phases.  At 4 (128 VGPRs,
-// all 4096 lanes of a GPU resident at once) the kernel carried 54 VGPR spills whose scratch traffic
-// was 12.7 MB of its 46.7 MB per v0 launch; the driver window runs at the same rate either way
-// (profiles/r3c_ab_occ3_regs3.txt, profiles/r3c_ab_occ3_trim.txt, profiles/r3c_traffic_occ3_trim.txt)
-#define MRP_STEP_WAVES_PER_EU 3
-#endif
 __global__ __launch_bounds__(BLOCK, MRP_STEP_WAVES_PER_EU) void k_step(uint32_t* state, int nl, const float* actions, float* obs, float* reward,
                                                 double* reward64, uint8_t* done_out, uint8_t* trunc_out, uint8_t* status_out, float* term_obs,
                                                 EnvParams P, uint64_t seed, uint64_t lane_offset, int auto_reset,
@@ -566,15 +553,15 @@ struct Launch {
                       float* obs, const EnvParams& P, uint64_t seed, uint64_t lane_offset) {
         hipLaunchKernelGGL(k_reset<ENV>, dim3(nl), dim3(BLOCK), 0, s, state, nl, mask, draws, actions, obs, P, seed, lane_offset);
     }
+    template <bool MULTI>
+    static void launch_step(hipStream_t s, const StepArgs& a) {
+        hipLaunchKernelGGL((k_step<ENV, MULTI>), dim3(a.nl), dim3(BLOCK), 0, s, a.state, a.nl, a.actions, a.obs, a.reward,
+                           a.reward64, a.done, a.trunc, a.status, a.term_obs, a.P, a.seed, a.lane_offset, a.auto_reset,
+                           a.max_steps, a.order, a.cost, a.costmax, MULTI ? a.nsteps : 1);
+    }
     static void step(hipStream_t s, const StepArgs& a) {
-        if (a.nsteps > 1)
-            hipLaunchKernelGGL((k_step<ENV, true>), dim3(a.nl), dim3(BLOCK), 0, s, a.state, a.nl, a.actions, a.obs, a.reward,
-                               a.reward64, a.done, a.trunc, a.status, a.term_obs, a.P, a.seed, a.lane_offset, a.auto_reset,
-                               a.max_steps, a.order, a.cost, a.costmax, a.nsteps);
-        else
-            hipLaunchKernelGGL((k_step<ENV, false>), dim3(a.nl), dim3(BLOCK), 0, s, a.state, a.nl, a.actions, a.obs, a.reward,
-                               a.reward64, a.done, a.trunc, a.status, a.term_obs, a.P, a.seed, a.lane_offset, a.auto_reset,
-                               a.max_steps, a.order, a.cost, a.costmax, 1);
+        if (a.nsteps > 1) launch_step<true>(s, a);
+        else launch_step<false>(s, a);
 #ifdef MRP_STAMPS
         hipLaunchKernelGGL(k_stamp_fold<ENV>, dim3(1), dim3(256), 0, s, a.nl);
 #endif
@@ -624,10 +611,8 @@ struct Launch {
     }
     static constexpr EnvOps ops() {
         using D = Dims<ENV>;
-        using LS = LaneState<ENV>;
-        return EnvOps{lane_words<ENV>(), (int)(offsetof(LS, toiEvents) / 4),
-                      {D::OBS, D::ACT, D::NDRAW, D::NA, D::NB, D::NF},
-                      StateIO<ENV>::P, LS::C, LS::NCA, StateIO<ENV>::HWW, MRP_STEP_WAVES_PER_EU, upload_tables, init, reset, step,
+        return EnvOps{lane_words<ENV>(), {D::OBS, D::ACT, D::NDRAW, D::NA, D::NB, D::NF}, MRP_STEP_WAVES_PER_EU,
+                      StateIO<ENV>::repair_marks, upload_tables, init, reset, step,
                       bodies, faults, counters, render, pixels, goals, debug_read, debug_progress};
     }
 };
@@ -643,95 +628,3 @@ struct Launch {
     namespace mrp { const EnvOps MRP_ENV_OPS_NAME(E) = Launch<E>::ops(); }
 #endif
 
-#if MRP_ENV == 0
-namespace {
-// Diagnostic micro-benchmark of the lane-distributed velocity sweeps (mrp_debug_velbench): a
-// synthetic v0 island of nc agent-block contacts with pcount manifold points each, swept `iters`
-// times with the early exit off; out[block] = s_memtime cycles of the sweeps.
-__global__ __launch_bounds__(BLOCK, MRP_STEP_WAVES_PER_EU) void k_velbench(int nc, int pcount, int iters, unsigned long long* out) {
-    using W = World<0>;
-    __shared__ Shared<0> sh;
-    const int tid = threadIdx.x;
-    EnvParams P{};
-    W w(sh, g_table, P, tid);
-    auto& is = sh.isl;
-    // nc >= 100: a chain of nc - 100 contacts (contact i between bodies i and i + 1, all moving)
-    const bool chain = nc >= 100;
-    if (chain) nc -= 100;
-    if (tid == 0) {
-        is.nb = nc + 1; is.nc = nc;
-        for (int b = 0; b <= nc; ++b) { is.vvx[b] = 0.3f * b - 0.1f; is.vvy[b] = 0.2f - 0.05f * b; is.vw[b] = b == 0 ? 0.01f : 0.0f; }
-        for (int i = 0; i < nc; ++i) {
-            VC& vc = sh.u.sol.vcs[i];
-            const float ang = 0.7f * (float)i + 0.3f;
-            vc.nx = __cosf(ang); vc.ny = __sinf(ang);
-            vc.iaI = i + 1; vc.ibI = 0; vc.mA = 1.0f; vc.iA = 0.0f; vc.mB = 0.05f; vc.iB = 1.0f / 17.0833f; vc.friction = 0.44f;
-            vc.pointCount = pcount;
-            if (chain) { vc.iaI = i; vc.ibI = i + 1; vc.mA = 1.0f; vc.iA = 0.05f; }
-            for (int j = 0; j < 2; ++j) {
-                vc.rAx[j] = 0.1f * j - 0.2f; vc.rAy[j] = 0.75f; vc.rBx[j] = 0.4f + 0.3f * j; vc.rBy[j] = -0.6f;
-                vc.ni[j] = 0.2f; vc.ti[j] = 0.01f; vc.vbias[j] = 0.0f; vc.nmass[j] = 0.9f; vc.tmass[j] = 0.8f;
-            }
-            vc.k0 = 1.2f; vc.k1 = 0.3f; vc.k3 = 1.1f; vc.nm0 = 0.9f; vc.nm1 = -0.2f; vc.nm3 = 0.95f;
-        }
-    }
-    __syncthreads();
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    int sw = nc == 1 ? w.solver_velocity_one(is, sh.u.sol.vcs, iters, false)
-                     : (nc == 2 ? w.solver_velocity_two(is, sh.u.sol.vcs, iters, false) : -1);
-    if (sw < 0) w.solver_velocity_lanes(is, sh.u.sol.vcs, iters, false);
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    __syncthreads();
-    if (tid == 0) out[blockIdx.x] = t1 - t0 + (is.vvx[0] == 12345.0f ? 1ull : 0ull);
-}
-// Diagnostic micro-benchmark of the position passes (mrp_debug_posbench): a synthetic island of nc
-// static-wall contacts of pcount points on one moving block (body 0), walls alternately above and
-// below it, each penetrating it by ~0.1 (the squeezed shape of the slowest v0 lanes: the passes never
-// reach the exit test), solved by the dispatch of the step (register paths for 1-2 contacts, the
-// lanes path above); out[2 * block] = s_memtime cycles, out[2 * block + 1] = passes run.
-__global__ __launch_bounds__(BLOCK, MRP_STEP_WAVES_PER_EU) void k_posbench(int nc, int pcount, int iters, unsigned long long* out) {
-    using W = World<0>;
-    __shared__ Shared<0> sh;
-    const int tid = threadIdx.x;
-    EnvParams P{};
-    W w(sh, g_table, P, tid);
-    auto& is = sh.isl;
-    if (tid == 0) {
-        is.nb = nc + 1; is.nc = nc;
-        is.pcx[0] = 0.0f; is.pcy[0] = 0.0f; is.pa[0] = 0.3f; is.vvx[0] = 0.0f; is.vvy[0] = 0.0f; is.vw[0] = 0.0f;
-        for (int i = 0; i < nc; ++i) {
-            const float up = (i & 1) ? -1.0f : 1.0f;   // wall above (normal down) or below (normal up)
-            is.pcx[i + 1] = 0.05f * (float)i; is.pcy[i + 1] = up; is.pa[i + 1] = 0.0f;
-            is.vvx[i + 1] = 0.0f; is.vvy[i + 1] = 0.0f; is.vw[i + 1] = 0.0f;
-            VC& vc = sh.u.sol.vcs[i];
-            PC& pc = sh.u.sol.pcs[i];
-            vc.iaI = i + 1; vc.ibI = 0; vc.mA = 0.0f; vc.iA = 0.0f; vc.mB = 0.05f; vc.iB = 1.0f / 17.0833f;
-            vc.pointCount = pcount;
-            pc.type = MT_FACEA; pc.pointCount = pcount;
-            pc.lnx = 0.0f; pc.lny = -up; pc.lpx0 = 0.0f; pc.lpy0 = -0.5f * up;
-            pc.lpx[0] = -0.2f; pc.lpy[0] = 0.62f * up; pc.lpx[1] = 0.2f; pc.lpy[1] = 0.6f * up;
-            pc.lcAx = 0.0f; pc.lcAy = 0.0f; pc.lcBx = 0.0f; pc.lcBy = 0.0f; pc.rA = 0.01f; pc.rB = 0.01f;
-        }
-    }
-    __syncthreads();
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    int n = w.solver_position_small(is, sh.u.sol.vcs, sh.u.sol.pcs, false, -1, -1, iters);
-    if (n < 0) n = w.solver_position_lanes(is, sh.u.sol.vcs, sh.u.sol.pcs, false, -1, -1, iters);
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    __syncthreads();
-    if (tid == 0) { out[2 * blockIdx.x] = t1 - t0 + (is.pcx[0] == 12345.0f ? 1ull : 0ull); out[2 * blockIdx.x + 1] = (unsigned long long)n; }
-}
-}  // namespace
-hipError_t mrp::posbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), &v0, sizeof(EnvTables));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_posbench, dim3(blocks), dim3(BLOCK), 0, nullptr, nc, pcount, iters, d_out);
-    return hipGetLastError();
-}
-hipError_t mrp::velbench_launch(const EnvTables& v0, int nc, int pcount, int iters, int blocks, unsigned long long* d_out) {
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_table), &v0, sizeof(EnvTables));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_velbench, dim3(blocks), dim3(BLOCK), 0, nullptr, nc, pcount, iters, d_out);
-    return hipGetLastError();
-}
-#endif

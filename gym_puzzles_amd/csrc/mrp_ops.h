@@ -56,12 +56,11 @@ enum : int { DBG_STAMPS = 0, DBG_PMAX = 1, DBG_STEPMAX = 2, DBG_RT = 3, DBG_TRAC
 
 struct EnvOps {
     int words;                 // lane_words<ENV>()
-    int counters_word;         // word offset of LaneState::toiEvents (followed by posIters)
     int dims[6];               // Dims<ENV>: OBS, ACT, NDRAW, NA, NB, NF (mrp_create checks them against the tables)
-    // contact-slot layout of LaneState (mrp_set_state repairs an understated high-water mark cHW):
-    // word offset of cnext (the first of `cslot_arrays` contiguous arrays of `cslot_n` words) and of cHW
-    int cslot_word, cslot_n, cslot_arrays, chw_word;
     int step_waves_per_eu;     // k_step's launch bound: resident waves per SIMD (mrp_create: resident lanes)
+    // host arithmetic on n_lanes lane states (mrp_set_state): raise every lane's contact high-water
+    // mark cHW to cover its non-initial slots (mrp_lane.h StateIO::repair_marks)
+    void (*repair_marks)(uint32_t* state, size_t n_lanes);
     hipError_t (*upload_tables)(const EnvTables& t);   // this env's tables -> its unit's __constant__ copy
     void (*init)(hipStream_t, uint32_t* state, int nl);
     void (*reset)(hipStream_t, uint32_t* state, int nl, const uint8_t* mask, const double* draws, const float* actions,

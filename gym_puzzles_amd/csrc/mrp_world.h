@@ -51,6 +51,12 @@ constexpr int NULLN = -1;
 //                     the lanes path (3+ contacts)
 // MRP_FRESH_REGS=1    values k_step needs late in the step are made where they are used, and the thread id
 //                     is made opaque per island and TOI pass (refresh_tid) (v0, v3)
+// MRP_CONTACT_GRANULES=1  k_step moves its live contact slots in 16-B granules, not words (mrp_lane.h StateIO; v2)
+// MRP_STEP_WAVES_PER_EU   k_step's launch bound, resident waves per SIMD.  Default 3 (168 VGPRs): k_step without
+//                     VGPR spills in the solver phases.  At 4 (128 VGPRs, all 4096 lanes of a GPU resident at
+//                     once: v0, v3) the kernel carried 54 VGPR spills whose scratch traffic was 12.7 MB of its
+//                     46.7 MB per v0 launch; the driver window runs at the same rate either way
+//                     (profiles/r3c_ab_occ3_regs3.txt, r3c_ab_occ3_trim.txt, r3c_traffic_occ3_trim.txt)
 // Diagnostic builds (never shipped): MRP_STAMPS (+ MRP_STAMPS_TOI) per-phase timing, MRP_PROGRESS
 // hang localisation.  The arms measured and dropped in rounds 3-5 are kept as patches under
 // profiles/ (r6_dropped_arms.patch), not in this header.
@@ -71,6 +77,12 @@ constexpr int NULLN = -1;
 #endif
 #ifndef MRP_FRESH_REGS
 #define MRP_FRESH_REGS 0
+#endif
+#ifndef MRP_CONTACT_GRANULES
+#define MRP_CONTACT_GRANULES 0
+#endif
+#ifndef MRP_STEP_WAVES_PER_EU
+#define MRP_STEP_WAVES_PER_EU 3
 #endif
 #if MRP_VEL_VTCROSS
 #define MRP_VT(dv, n, t) pcross(dv, n)
@@ -216,6 +228,13 @@ template <int ENV> struct alignas(16) LaneState {   // 16-B granules: moved with
 };
 
 template <int ENV> constexpr int lane_words() { return (int)(sizeof(LaneState<ENV>) / 4); }
+
+// The initial contents of the contact slots, the one statement of the rule behind LaneState::cHW:
+// word i of the contact region (NCA arrays of C words from cnext on; slot i % C of array i / C).
+// cnext (array 0) chains the free list 0 -> 1 -> ... -> C-1 -> NULLN; every other array is 0.
+MRP_HD constexpr uint32_t contact_slot_init(int i, int C) {
+    return i < C ? (i + 1 < C ? (uint32_t)(i + 1) : (uint32_t)NULLN) : 0u;
+}
 
 struct TOIOut { int state; float t; };
 

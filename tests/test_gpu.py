@@ -539,17 +539,20 @@ def test_frameskip_parity(gpu_lib, orc, env_id, frameskip):
     b.close()
 
 
-def test_set_state_repairs_understated_contact_mark(gpu_lib):
+@pytest.mark.parametrize("env_id", [0, 2])
+def test_set_state_repairs_understated_contact_mark(gpu_lib, env_id):
     """k_step moves only the contact slots below LaneState::cHW; a state injected through
     mrp_set_state with that mark understated (here zeroed on every lane) must not lose its live
     contacts: mrp_set_state recomputes the mark from the slots, so the lanes step exactly as from
-    the unmodified state."""
+    the unmodified state.  Env 0 moves its live slots word by word, env 2 in 16-B granules; the
+    oracle's device-RNG rollout of seed 41 holds contacts (5 / 17 slots) in both at step 40, with
+    no lane reset before it.  tests/test_lane_repair.py checks the repair's arithmetic on the host."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from lane_layout import offsets
-    a, b = _twin(0, 64, seed=41, warm=40)
+    a, b = _twin(env_id, 64, seed=41, warm=40)
     snap = a.get_state().copy()
-    off, _ = offsets(0)
+    off, _ = offsets(env_id)
     assert (snap[:, off["cHW"]] > 0).any(), "no lane holds a contact slot: the test needs a live contact"
     bad = snap.copy()
     bad[:, off["cHW"]] = 0
