@@ -10,8 +10,12 @@ gym_puzzles env interface.  See DESIGN.md.
     pixels                 the numpy restatement of the pixel observations (Batch.pixels, obs_type="image")
     DeviceRolloutBuffer    SB3 RolloutBuffer on the device: TimeLimit bootstrap + GAE in one launch
                            (rollout.gae_device; rollout.gae_ref is the numpy restatement of the rule)
+    DevicePolicy           SB3 ActorCriticPolicy (MlpExtractor) on the device: forward, sampling, log-prob, value
+                           and clipping in one launch (policy.policy_ref / tanh_ref state the rule in numpy);
+                           rollout.collect_rollouts runs act / step / normalise / add without a host sync
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
+from .policy import policy_ref, tanh_ref  # noqa: F401  (pure numpy)
 
 
 def __getattr__(name):
@@ -26,4 +30,10 @@ def __getattr__(name):
     if name == "DeviceRolloutBuffer":
         from . import rollout
         return rollout.DeviceRolloutBuffer
+    if name == "DevicePolicy":
+        from . import policy
+        return policy.DevicePolicy
+    if name == "collect_rollouts":
+        from . import rollout
+        return rollout.collect_rollouts
     raise AttributeError(name)

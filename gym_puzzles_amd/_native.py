@@ -89,6 +89,13 @@ ABI = {
     "mrp_norm_get_stats": (_i, [_P, _P]),
     "mrp_norm_set_stats": (_i, [_P, _P]),
     "mrp_gae_device": (_i, [_i, _P, _i, _i] + [_P] * 7 + [_d, _d, _P, _P]),
+    "mrp_policy_create": (_i, [_i] * 6 + [_ip, _i, _PP]),
+    "mrp_policy_destroy": (None, [_P]),
+    "mrp_policy_last_error": (ctypes.c_char_p, [_P]),
+    "mrp_policy_set_params": (_i, [_P, _PP, _PP, _P, _P]),
+    "mrp_policy_act_device": (_i, [_P, _P, _i, _P, _P, _u64, _u64, _u64, _i] + [_P] * 5),
+    "mrp_policy_values_device": (_i, [_P, _P, _i, _P, _P]),
+    "mrp_selftest_tanh": (_i, [_i, _P, _P, _i]),
 }
 EXPORTED = tuple(ABI)
 

@@ -24,12 +24,17 @@ with open(os.path.join(CSRC, "mrp_config.h")) as _f:   # the rows of MRP_ENV_LIS
 # (source in csrc/, object name, env id of an env unit or None): the shared units, then one object per id
 SOURCES = ([(f, f + ".o", None) for f in ("mrp_kernels.hip", "mrp_tables.cpp", "mrp_norm.hip")]
            + [("mrp_unit.hip", f"mrp_env{e}.o", e) for e in range(N_ENVS)])
+# The device policy's unit (csrc/mrp_policy.hip) is compiled and linked like the units above.  It stands
+# in a list of its own: SOURCES is "the three shared units plus one object per env id" wherever the
+# registry is checked or an A/B library picks its units.
+POLICY_SOURCES = [("mrp_policy.hip", "mrp_policy.hip.o", None)]
+UNITS = SOURCES + POLICY_SOURCES
 HEADERS = ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h", "mrp_ops.h", "mrp_lane.h", "mrp_render.h",
            "mrp_pixels.h", "mrp_microbench.h")
 
 
 def deps(csrc: str = CSRC) -> list[str]:
-    return [os.path.join(csrc, f) for f in sorted({s for s, _, _ in SOURCES}) + list(HEADERS)] + [
+    return [os.path.join(csrc, f) for f in sorted({s for s, _, _ in UNITS}) + list(HEADERS)] + [
         os.path.join(HERE, "..", "include", "mrp.h"), os.path.abspath(__file__)]
 
 
@@ -135,20 +140,20 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
     objdir = os.path.join(HERE, "build", os.path.basename(out) + ".obj")
     os.makedirs(objdir, exist_ok=True)
     dflags = [f"-D{d}" for d in defines]
-    srcs = [os.path.join(csrc, s) for s, _, _ in SOURCES]
-    objs = [os.path.join(objdir, o) for _, o, _ in SOURCES]
-    todo = list(range(len(SOURCES)))
+    srcs = [os.path.join(csrc, s) for s, _, _ in UNITS]
+    objs = [os.path.join(objdir, o) for _, o, _ in UNITS]
+    todo = list(range(len(UNITS)))
     dep_files = deps(csrc)
     if only_envs is not None:
         assert out != OUT, "only_envs builds a variant library, never the default one"
         base = os.path.join(HERE, "build", os.path.basename(OUT) + ".obj")
-        todo = [i for i, (_, _, e) in enumerate(SOURCES) if e is None or e in only_envs]
+        todo = [i for i, (_, _, e) in enumerate(UNITS) if e is None or e in only_envs]
         # the reused objects must have been compiled from the current sources and headers: an env
         # unit built before a shared header changed would mix two layouts in one A/B library
         # (MRP_ALLOW_STALE_UNITS=1 accepts it for an A/B of the listed envs when the edit leaves the
         # LaneState / EnvOps layout unchanged; mrp_create still checks each unit's compiled dims)
         newest_dep = max(os.path.getmtime(d) for d in dep_files if os.path.exists(d) and d.endswith((".h", ".hip", ".cpp")))
-        for i, (_, o, _) in enumerate(SOURCES):
+        for i, (_, o, _) in enumerate(UNITS):
             if i not in todo:
                 objs[i] = os.path.join(base, o)
                 if not os.path.exists(objs[i]):
@@ -164,7 +169,7 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
     newest_header = max(os.path.getmtime(d) for d in headers if os.path.exists(d))
 
     def compile_one(i: int) -> None:
-        env = SOURCES[i][2]
+        env = UNITS[i][2]
         unit = [] if env is None else (UNIT_FLAGS.get(env, []) if not extra else []) + [f"-DMRP_ENV={env}"]
         cmd = [hipcc()] + FLAGS + unit + extra + dflags + ["-c", srcs[i], "-o", objs[i]]
         # incremental: an object newer than its source and every header, built with the same command
@@ -185,8 +190,8 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, defines=()
             f.write(line)
 
     # slowest units first; each hipcc is single-threaded, so one job per core
-    jobs = jobs or max(1, min(len(SOURCES), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", "16"))))
-    order = sorted(todo, key=lambda i: SOURCES[i][2] is None)
+    jobs = jobs or max(1, min(len(UNITS), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", "16"))))
+    order = sorted(todo, key=lambda i: UNITS[i][2] is None)
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(compile_one, order))
     cmd = [hipcc()] + FLAGS + ["-shared"] + objs + ["-o", out + ".tmp"]

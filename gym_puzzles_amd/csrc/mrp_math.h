@@ -281,6 +281,51 @@ MRP_HD Rot rot_z(float y) {
 }
 
 // ---------------------------------------------------------------------------------------
+// tanh for the policy's activations: a float32 -> float32 rule of this build (no library tanh on
+// either side), restated operation for operation by gym_puzzles_amd.policy.tanh_ref.  Like rot()
+// it works in float64 with every operation rounded on its own (-ffp-contract=off; only + - * /,
+// comparisons, integer conversion and exponent bits) and rounds to float32 once:
+//   y = -2|x|, n = nearest integer to y / ln 2 (ties away), r = (y - n ln2_hi) - n ln2_lo,
+//   p = expm1(r) by its Taylor polynomial of degree 11 (|r| <= 0.35: remainder 2e-14 relative),
+//   E = 2^n (1 + p) = exp(-2|x|); tanh|x| = (1 - E) / (1 + E), and for n = 0 the same quotient as
+//   -p / (2 + p), which has no cancellation, so subnormal inputs keep their relative accuracy.
+// The reciprocal of the denominator is the correctly rounded float32 1 / (float)den refined by two
+// Newton steps in float64 (no float64 division, whose lowering differs between targets).
+// |x| >= 20 (inf included) gives +-1 (float32 tanh is 1 from 9.02 on), NaN comes back unchanged,
+// +-0 comes back with its sign.  Error against the real tanh: 0.5 ulp + 2^-25 (measured maximum
+// in DESIGN.md "Device policy").
+// ---------------------------------------------------------------------------------------
+constexpr double TH_INV_LN2 = 0x1.71547652b82fep+0, TH_LN2_HI = 0x1.62e42feep-1, TH_LN2_LO = 0x1.a39ef35793c76p-33;
+constexpr double TH_C2 = 1.0 / 2, TH_C3 = 1.0 / 6, TH_C4 = 1.0 / 24, TH_C5 = 1.0 / 120, TH_C6 = 1.0 / 720,
+                 TH_C7 = 1.0 / 5040, TH_C8 = 1.0 / 40320, TH_C9 = 1.0 / 362880, TH_C10 = 1.0 / 3628800,
+                 TH_C11 = 1.0 / 39916800;
+
+MRP_HD double u2d(uint64_t u) { union { double d; uint64_t u; } x; x.u = u; return x.d; }
+
+MRP_HD float tanh_f32(float x) {
+    const uint32_t ux = f2u(x), ax = ux & 0x7fffffffu;
+    const bool nan = ax > 0x7f800000u;
+    const float xa = u2f(ax);
+    const bool sat = !(xa < 20.0f);                    // also inf and NaN: the arithmetic below stays in range
+    const double y = -2.0 * (double)(sat ? 20.0f : xa);
+    const int n = (int)(y * TH_INV_LN2 - 0.5);         // y <= 0: truncation rounds to nearest, ties away
+    const double dn = (double)n;
+    const double r = (y - dn * TH_LN2_HI) - dn * TH_LN2_LO;
+    double q = TH_C11;
+    q = q * r + TH_C10; q = q * r + TH_C9; q = q * r + TH_C8; q = q * r + TH_C7; q = q * r + TH_C6;
+    q = q * r + TH_C5; q = q * r + TH_C4; q = q * r + TH_C3; q = q * r + TH_C2;
+    const double p = r + (r * r) * q;
+    const double E = u2d((uint64_t)(1023 + n) << 52) * (1.0 + p);
+    const double num = n == 0 ? -p : 1.0 - E;
+    const double den = n == 0 ? 2.0 + p : 1.0 + E;
+    const double r0 = (double)(1.0f / (float)den);
+    const double r1 = r0 * (2.0 - den * r0);
+    const double r2 = r1 * (2.0 - den * r1);
+    const float t = sat ? 1.0f : (float)(num * r2);
+    return nan ? x : u2f((f2u(t) & 0x7fffffffu) | (ux & 0x80000000u));
+}
+
+// ---------------------------------------------------------------------------------------
 // Counter-based RNG for on-device resets and synthetic actions (pure integer SplitMix64
 // mixing; identical on host and device, so the CPU oracle can replay device resets).
 // ---------------------------------------------------------------------------------------

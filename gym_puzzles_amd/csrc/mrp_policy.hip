@@ -1,0 +1,436 @@
+// mrp_policy.hip -- SB3's ActorCriticPolicy with MlpExtractor on the device: forward pass,
+// diagonal-Gaussian sampling, log-prob, value and action clipping for a batch of lanes in ONE
+// launch (DESIGN.md "Device policy").  The rule, which k_policy matches bit for bit, is
+// gym_puzzles_amd/policy.py's policy_ref:
+//   linear  : y[j] = fma(x[K-1], W[j][K-1], ... fma(x[0], W[j][0], b[j])), float32, k ascending
+//   act     : tanh_f32 (mrp_math.h) or max(x, 0)
+//   sample  : action = mean + std * eps; clipped = min(max(action, -1), 1);
+//             log_prob = sum_i ((-(d_i * d_i)) / (2 * (std_i * std_i)) - log_std_i) - log(sqrt(2 pi)),
+//             d = action - mean, the sum ascending from +0, every operation float32 and rounded alone
+//
+// Kernel shape: a workgroup of 4 waves takes a tile of 32 lanes through the whole network.  The
+// activations of a layer live in LDS ([32][LDA] float, three buffers: the trunk's output stays while
+// the policy tower runs); a hidden layer is v_mfma_f32_32x32x2_f32 with the bias as the initial
+// accumulator -- on gfx950 that instruction is bit for bit the k-ordered fmaf chain of the rule --
+// each wave owning the 32-column tiles w, w + 4, ... of the layer's output.  The weights were packed
+// at set_params into [K][Npad] (Npad a multiple of 32, pad columns zero), so a wave's B operand of
+// one k-step is two contiguous 128-byte rows streamed from L2.  An odd K's last term is an explicit
+// fmaf on the accumulator registers (a zero pad k-step would turn an accumulator of -0 into +0).
+// The narrow heads (act_dim, 1 outputs) are explicit fmaf chains on the VALU over torch's [out][in]
+// rows, and the epilogue runs in the same launch.  Rows past n_lanes compute on zero observations
+// and write nothing.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/mrp.h"
+#include "mrp_math.h"
+
+namespace {
+
+constexpr int P_NT = 256;        // 4 waves
+constexpr int P_TILE = 32;       // lanes (rows) per workgroup
+constexpr int P_LDA = 258;       // LDS row stride in floats: rows land 2 banks apart, so the A read
+                                 // (32 rows x 2 consecutive k) touches 64 different banks
+constexpr int P_MAXW = 256, P_MAXA = 16, P_MAXL = 4;
+constexpr int P_U = 8;          // k-steps of a hidden layer whose operands are in flight together
+constexpr int P_HS = P_MAXA + 1; // head outputs per row: act_dim means, then the value
+constexpr int STREAM_U1 = 4, STREAM_U2 = 5;   // rng_u01 stream ids (1-3: resets and synthetic actions)
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Layer { const float* w; const float* b; int K, N, Npad; };   // w packed [K][Npad], b [Npad]
+struct Head { const float* w; const float* b; int K, Kpad; };        // w [out][Kpad]: torch's rows, padded to 4 floats
+struct Net {
+    int obs_dim, act_dim, n_shared, n_pi, n_vf, relu;
+    Layer shared[P_MAXL], pi[P_MAXL], vf[P_MAXL];
+    Head act, val;
+    const float* log_std; const float* std;
+};
+
+__device__ __forceinline__ float activate(float v, int relu) { return relu ? mrp::fmax_(v, 0.0f) : mrp::tanh_f32(v); }
+
+// dst[32][N] = act(src[32][K] . W + b); src and dst are different LDS buffers
+__device__ __forceinline__ void hidden_layer(const Layer& L, const float* __restrict__ src, float* __restrict__ dst, int relu) {
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 31, h = l >> 5;
+    const int K2 = L.K & ~1, ntiles = L.Npad >> 5;
+    const float* ap = src + c * P_LDA + h;                 // A[i = l & 31][k = l >> 5]
+    for (int t = wave; t < ntiles; t += 4) {
+        const int col = t * 32 + c;
+        const float* wp = L.w + (size_t)h * L.Npad + col;  // B[k = l >> 5][j = l & 31]
+        const float bias = L.b[col];
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias;
+        // k-steps in chunks of P_U: the next chunk's operands are requested before the chunk in hand
+        // runs, so the L2 latency of a B row hides behind P_U matrix instructions of 64 cycles each
+        const int nchunk = K2 / (2 * P_U);
+        float a0[P_U], b0[P_U], a1[P_U] = {}, b1[P_U] = {};
+        if (nchunk > 0) {
+#pragma unroll
+            for (int u = 0; u < P_U; ++u) { a0[u] = ap[2 * u]; b0[u] = wp[(size_t)(2 * u) * L.Npad]; }
+        }
+        int k = 0;
+        for (int ch = 0; ch < nchunk; ++ch, k += 2 * P_U) {
+            if (ch + 1 < nchunk) {
+#pragma unroll
+                for (int u = 0; u < P_U; ++u) {
+                    a1[u] = ap[k + 2 * (P_U + u)];
+                    b1[u] = wp[(size_t)(k + 2 * (P_U + u)) * L.Npad];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < P_U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc, 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < P_U; ++u) { a0[u] = a1[u]; b0[u] = b1[u]; }
+        }
+        // the last, partial chunk: its loads go out together (an index past the end reads k-step 0 again
+        // and is not used), its matrix instructions run under wave-uniform tests
+#pragma unroll
+        for (int u = 0; u < P_U; ++u) {
+            const int kk = k + 2 * u < K2 ? k + 2 * u : 0;
+            a0[u] = ap[kk]; b0[u] = wp[(size_t)kk * L.Npad];
+        }
+#pragma unroll
+        for (int u = 0; u < P_U; ++u)
+            if (k + 2 * u < K2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc, 0, 0, 0);
+        // C/D: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+        if (L.K & 1) {
+            const float wv = L.w[(size_t)K2 * L.Npad + col];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                acc[r] = __builtin_fmaf(src[row * P_LDA + K2], wv, acc[r]);
+            }
+        }
+        if (col < L.N) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                dst[row * P_LDA + col] = activate(acc[r], relu);
+            }
+        }
+    }
+}
+
+// out[row][o0 + o] = fmaf chain over src[row][0..K) and row o of w, from b[o]; 32 rows x 8 outputs at a time.
+// The rows of w are padded to Kpad (a multiple of 4) in the device image, so 4 weights come per load.
+__device__ __forceinline__ void head(const Head& H, int n_out, const float* __restrict__ src, float* __restrict__ out, int o0) {
+    const int row = threadIdx.x & 31, nq = H.K >> 2;
+    const float* x = src + row * P_LDA;
+    for (int o = threadIdx.x >> 5; o < n_out; o += P_NT / 32) {
+        const float* w = H.w + (size_t)o * H.Kpad;
+        const float4* w4 = reinterpret_cast<const float4*>(w);
+        float acc = H.b[o];
+        int q = 0;
+        for (; q + P_U <= nq; q += P_U) {
+            float4 wv[P_U];
+#pragma unroll
+            for (int u = 0; u < P_U; ++u) wv[u] = w4[q + u];
+#pragma unroll
+            for (int u = 0; u < P_U; ++u) {
+                const float* xk = x + 4 * (q + u);
+                acc = __builtin_fmaf(xk[0], wv[u].x, acc);
+                acc = __builtin_fmaf(xk[1], wv[u].y, acc);
+                acc = __builtin_fmaf(xk[2], wv[u].z, acc);
+                acc = __builtin_fmaf(xk[3], wv[u].w, acc);
+            }
+        }
+        for (int k = 4 * q; k < H.K; ++k) acc = __builtin_fmaf(x[k], w[k], acc);
+        out[row * P_HS + o0 + o] = acc;
+    }
+}
+
+// a tower of n layers from buffer `in`, writing alternately to buffers a and b; returns the buffer of its output
+__device__ __forceinline__ int tower(const Layer* L, int n, float* lds, int in, int a, int b, int relu) {
+    for (int i = 0; i < n; ++i) {
+        const int out = (i & 1) ? b : a;
+        hidden_layer(L[i], lds + in * (P_TILE * P_LDA), lds + out * (P_TILE * P_LDA), relu);
+        __syncthreads();
+        in = out;
+    }
+    return in;
+}
+
+__global__ __launch_bounds__(P_NT) void k_policy(const Net net, int n_lanes, const float* __restrict__ obs,
+                                                 const float* __restrict__ eps_in, uint64_t seed, uint64_t lane_offset,
+                                                 uint64_t counter, int deterministic, int values_only,
+                                                 float* __restrict__ actions, float* __restrict__ clipped,
+                                                 float* __restrict__ values, float* __restrict__ log_probs,
+                                                 float* __restrict__ eps_out) {
+    __shared__ float lds[3 * P_TILE * P_LDA];
+    __shared__ float hs[P_TILE * P_HS];     // the heads' outputs, then the log-prob terms
+    const int tid = threadIdx.x, base = blockIdx.x * P_TILE;
+    const int D = net.obs_dim, A = net.act_dim, relu = net.relu;
+    for (int e = tid; e < P_TILE * D; e += P_NT) {
+        const int row = e / D, k = e - row * D;
+        const int lane = base + row;
+        lds[row * P_LDA + k] = lane < n_lanes ? obs[(size_t)lane * D + k] : 0.0f;
+    }
+    __syncthreads();
+    const int T = tower(net.shared, net.n_shared, lds, 0, 1, 0, relu);   // the trunk ping-pongs in buffers 0 and 1
+    if (!values_only) {
+        const int po = tower(net.pi, net.n_pi, lds, T, 1 - T, 2, relu);
+        head(net.act, A, lds + po * (P_TILE * P_LDA), hs, 0);
+        __syncthreads();                                                 // the value tower reuses the policy tower's buffers
+    }
+    const int vo = tower(net.vf, net.n_vf, lds, T, 1 - T, 2, relu);
+    head(net.val, 1, lds + vo * (P_TILE * P_LDA), hs, P_MAXA);
+    __syncthreads();
+    const int row = tid & 31, lane = base + row;
+    if (values && tid < P_TILE && lane < n_lanes) values[lane] = hs[row * P_HS + P_MAXA];
+    if (values_only) return;
+    float term[(P_MAXA + 7) / 8];
+#pragma unroll
+    for (int s = 0; s < (P_MAXA + 7) / 8; ++s) {
+        const int i = (tid >> 5) + 8 * s;
+        term[s] = 0.0f;
+        if (i < A && lane < n_lanes) {
+            const size_t e = (size_t)lane * A + i;
+            const float m = hs[row * P_HS + i];
+            const float sd = net.std[i];
+            float eps = 0.0f, a = m;
+            if (!deterministic) {
+                if (eps_in) {
+                    eps = eps_in[e];
+                } else {   // Box-Muller in float64, u1 in (0, 1]
+                    const uint64_t ctr = counter * (uint64_t)A + (uint64_t)i, gl = lane_offset + (uint64_t)lane;
+                    const double u1 = 1.0 - mrp::rng_u01(seed, gl, STREAM_U1, ctr), u2 = mrp::rng_u01(seed, gl, STREAM_U2, ctr);
+                    eps = (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+                }
+                a = m + sd * eps;
+            }
+            if (eps_out) eps_out[e] = eps;
+            actions[e] = a;
+            if (clipped) clipped[e] = mrp::fmin_(mrp::fmax_(a, -1.0f), 1.0f);
+            const float d = a - m;
+            const float q = (-(d * d)) / (2.0f * (sd * sd));
+            term[s] = (q - net.log_std[i]) - 0x1.d67f1cp-1f;   // float32(log(sqrt(2 pi)))
+        }
+    }
+    __syncthreads();                       // every mean has been read: hs now takes the terms
+#pragma unroll
+    for (int s = 0; s < (P_MAXA + 7) / 8; ++s) {
+        const int i = (tid >> 5) + 8 * s;
+        if (i < A) hs[row * P_HS + i] = term[s];
+    }
+    __syncthreads();
+    if (tid < P_TILE && lane < n_lanes && log_probs) {
+        float sum = 0.0f;
+        for (int i = 0; i < A; ++i) sum = sum + hs[row * P_HS + i];
+        log_probs[lane] = sum;
+    }
+}
+
+__global__ void k_tanh(const float* __restrict__ x, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = mrp::tanh_f32(x[i]);
+}
+
+thread_local std::string g_policy_create_error;
+
+}  // namespace
+
+struct mrp_policy {
+    int device = 0, ready = 0, n_layers = 0;
+    int widths[3 * P_MAXL] = {};
+    Net net = {};
+    float* d_params = nullptr;
+    size_t n_floats = 0;
+    std::string err;
+};
+
+#define PCHK(p, expr)                                                      \
+    do {                                                                   \
+        hipError_t _e = (expr);                                            \
+        if (_e != hipSuccess) {                                            \
+            (p)->err = std::string(#expr) + ": " + hipGetErrorString(_e);  \
+            return MRP_E_HIP;                                              \
+        }                                                                  \
+    } while (0)
+
+namespace {
+
+inline int pad32(int n) { return (n + 31) & ~31; }
+
+// the device image of the parameters: per hidden layer the packed weights [K][Npad] and bias [Npad],
+// then the heads' rows (padded to 4 floats), log_std and std; fills the Net's pointers relative to `base`
+size_t layout(mrp_policy* p, float* base) {
+    Net& n = p->net;
+    size_t off = 0;
+    auto take = [&](size_t count) { float* q = base ? base + off : nullptr; off += (count + 3) & ~(size_t)3; return q; };
+    int li = 0;
+    auto towers = [&](Layer* L, int count, int K) {
+        for (int i = 0; i < count; ++i, ++li) {
+            L[i].K = K; L[i].N = p->widths[li]; L[i].Npad = pad32(L[i].N);
+            L[i].w = take((size_t)K * L[i].Npad);
+            L[i].b = take(L[i].Npad);
+            K = L[i].N;
+        }
+        return K;
+    };
+    const int kt = towers(n.shared, n.n_shared, n.obs_dim);
+    n.act.K = towers(n.pi, n.n_pi, kt);
+    n.val.K = towers(n.vf, n.n_vf, kt);
+    n.act.Kpad = (n.act.K + 3) & ~3; n.val.Kpad = (n.val.K + 3) & ~3;
+    n.act.w = take((size_t)n.act_dim * n.act.Kpad); n.act.b = take(n.act_dim);
+    n.val.w = take(n.val.Kpad); n.val.b = take(1);
+    n.log_std = take(n.act_dim); n.std = take(n.act_dim);
+    return off;
+}
+
+int policy_launch(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, const float* d_eps_in, uint64_t seed,
+                  uint64_t lane_offset, uint64_t counter, int deterministic, int values_only, float* d_actions, float* d_clipped,
+                  float* d_values, float* d_log_probs, float* d_eps_out) {
+    PCHK(p, hipSetDevice(p->device));
+    const dim3 grid((unsigned)(((long long)n_lanes + P_TILE - 1) / P_TILE)), block(P_NT);
+    hipLaunchKernelGGL(k_policy, grid, block, 0, (hipStream_t)hip_stream, p->net, n_lanes, d_obs, d_eps_in, seed, lane_offset,
+                       counter, deterministic, values_only, d_actions, d_clipped, d_values, d_log_probs, d_eps_out);
+    PCHK(p, hipGetLastError());
+    return MRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* mrp_policy_last_error(const mrp_policy* p) { return p ? p->err.c_str() : g_policy_create_error.c_str(); }
+
+void mrp_policy_destroy(mrp_policy* p) {
+    if (!p) return;
+    if (p->d_params) {
+        (void)hipSetDevice(p->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p->d_params);
+    }
+    delete p;
+}
+
+int mrp_policy_create(int device, int obs_dim, int act_dim, int n_shared, int n_pi, int n_vf, const int* widths, int activation,
+                      mrp_policy** out) {
+    std::string& err = g_policy_create_error;
+    err.clear();
+    auto bad = [&](const char* what) { err = std::string("mrp_policy_create: ") + what; return MRP_E_ARG; };
+    if (!out) return bad("null out");
+    *out = nullptr;
+    if (obs_dim < 1 || obs_dim > P_MAXW) return bad("obs_dim outside 1..256");
+    if (act_dim < 1 || act_dim > P_MAXA) return bad("act_dim outside 1..16");
+    if (n_shared < 0 || n_pi < 0 || n_vf < 0 || n_shared + (n_pi > n_vf ? n_pi : n_vf) > P_MAXL)
+        return bad("layer counts: n_shared + max(n_pi, n_vf) must be 0..4");
+    if (activation != MRP_POLICY_TANH && activation != MRP_POLICY_RELU) return bad("activation is neither tanh nor relu");
+    const int nl = n_shared + n_pi + n_vf;
+    if (nl > 0 && !widths) return bad("null widths");
+    for (int i = 0; i < nl; ++i)
+        if (widths[i] < 1 || widths[i] > P_MAXW) return bad("a layer width outside 1..256");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        err = "no HIP device available (no CPU fallback)";
+        return MRP_E_HIP;
+    }
+    if (device < 0 || device >= ndev) return bad("device index out of range");
+    mrp_policy* p = new (std::nothrow) mrp_policy();
+    if (!p) return bad("out of host memory");
+    p->device = device; p->n_layers = nl;
+    for (int i = 0; i < nl; ++i) p->widths[i] = widths[i];
+    p->net.obs_dim = obs_dim; p->net.act_dim = act_dim; p->net.n_shared = n_shared; p->net.n_pi = n_pi; p->net.n_vf = n_vf;
+    p->net.relu = activation == MRP_POLICY_RELU;
+    p->n_floats = layout(p, nullptr);
+    hipError_t e;
+    if ((e = hipSetDevice(device)) != hipSuccess || (e = hipMalloc(&p->d_params, p->n_floats * sizeof(float))) != hipSuccess) {
+        err = std::string("mrp_policy_create: ") + hipGetErrorString(e);
+        p->d_params = nullptr;
+        mrp_policy_destroy(p);
+        return MRP_E_HIP;
+    }
+    layout(p, p->d_params);
+    *out = p;
+    return MRP_OK;
+}
+
+int mrp_policy_set_params(mrp_policy* p, const float* const* weights, const float* const* biases, const float* log_std,
+                          const float* std) {
+    if (!p) return MRP_E_ARG;
+    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_set_params: ") + what; return MRP_E_ARG; };
+    if (!weights || !biases || !log_std || !std) return bad("null pointer");
+    for (int i = 0; i < p->n_layers + 2; ++i)
+        if (!weights[i] || !biases[i]) return bad("null layer pointer");
+    const Net& n = p->net;
+    std::vector<float> h(p->n_floats, 0.0f);
+    float* d0 = p->d_params;
+    auto at = [&](const float* dev) { return h.data() + (dev - d0); };
+    int li = 0;
+    auto pack = [&](const Layer* L, int count) {
+        for (int i = 0; i < count; ++i, ++li) {
+            float* w = at(L[i].w);
+            float* b = at(L[i].b);
+            for (int j = 0; j < L[i].N; ++j) {
+                for (int k = 0; k < L[i].K; ++k) w[(size_t)k * L[i].Npad + j] = weights[li][(size_t)j * L[i].K + k];
+                b[j] = biases[li][j];
+            }
+        }
+    };
+    pack(n.shared, n.n_shared); pack(n.pi, n.n_pi); pack(n.vf, n.n_vf);
+    for (int o = 0; o < n.act_dim; ++o)
+        for (int k = 0; k < n.act.K; ++k) at(n.act.w)[(size_t)o * n.act.Kpad + k] = weights[li][(size_t)o * n.act.K + k];
+    for (int e = 0; e < n.val.K; ++e) at(n.val.w)[e] = weights[li + 1][e];
+    for (int i = 0; i < n.act_dim; ++i) {
+        at(n.act.b)[i] = biases[li][i];
+        at(n.log_std)[i] = log_std[i];
+        at(n.std)[i] = std[i];
+    }
+    at(n.val.b)[0] = biases[li + 1][0];
+    PCHK(p, hipSetDevice(p->device));
+    PCHK(p, hipDeviceSynchronize());   // no launch still reads the old parameters
+    PCHK(p, hipMemcpy(p->d_params, h.data(), p->n_floats * sizeof(float), hipMemcpyHostToDevice));
+    p->ready = 1;
+    return MRP_OK;
+}
+
+int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, const float* d_eps_in, uint64_t seed,
+                          uint64_t lane_offset, uint64_t counter, int deterministic, float* d_actions, float* d_clipped,
+                          float* d_values, float* d_log_probs, float* d_eps_out) {
+    if (!p) return MRP_E_ARG;
+    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_act_device: ") + what; return MRP_E_ARG; };
+    if (n_lanes < 1) return bad("n_lanes < 1");
+    if (!d_obs || !d_actions) return bad("null pointer");
+    float* outs[] = {d_actions, d_clipped, d_values, d_log_probs, d_eps_out};
+    for (int i = 0; i < 5; ++i) {
+        if (!outs[i]) continue;
+        if (outs[i] == d_obs || outs[i] == d_eps_in) return bad("an output aliases an input");
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return bad("two outputs are the same array");
+    }
+    if (!p->ready) { p->err = "mrp_policy_act_device: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    return policy_launch(p, hip_stream, n_lanes, d_obs, d_eps_in, seed, lane_offset, counter, deterministic ? 1 : 0, 0, d_actions,
+                         d_clipped, d_values, d_log_probs, d_eps_out);
+}
+
+int mrp_policy_values_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, float* d_values) {
+    if (!p) return MRP_E_ARG;
+    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_values_device: ") + what; return MRP_E_ARG; };
+    if (n_lanes < 1) return bad("n_lanes < 1");
+    if (!d_obs || !d_values) return bad("null pointer");
+    if (d_values == d_obs) return bad("the output aliases the input");
+    if (!p->ready) { p->err = "mrp_policy_values_device: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    return policy_launch(p, hip_stream, n_lanes, d_obs, nullptr, 0, 0, 0, 1, 1, nullptr, nullptr, d_values, nullptr, nullptr);
+}
+
+int mrp_selftest_tanh(int device, const float* x, float* out, int n) {
+    if (!x || !out || n <= 0) return MRP_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
+    float *dx = nullptr, *dy = nullptr;
+    const size_t bytes = (size_t)n * sizeof(float);
+    int rc = MRP_E_HIP;
+    if (hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&dy, bytes) == hipSuccess &&
+        hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_tanh, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = MRP_OK;
+    }
+    if (dx) (void)hipFree(dx);
+    if (dy) (void)hipFree(dy);
+    return rc;
+}
+
+}  // extern "C"

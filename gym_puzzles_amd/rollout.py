@@ -110,6 +110,50 @@ def gae_device(rewards, values, episode_starts, last_values, dones, gamma, gae_l
     return advantages, returns
 
 
+def collect_rollouts(env, policy, buffer, obs, episode_start, norm=None, eps_out=None):
+    """SB3's ``OnPolicyAlgorithm.collect_rollouts`` on the device, ``buffer.n_steps`` iterations with no
+    host synchronisation: ``policy.act`` (a ``policy.DevicePolicy``), ``env.step_torch`` with the clipped
+    actions, the optional ``DeviceVecNormalize.step`` (``norm``), ``policy.values`` at the terminal
+    observations, ``buffer.add``; then ``last_values`` and ``compute_returns_and_advantage``.
+
+    ``obs`` float32 [N, obs_dim] and ``episode_start`` uint8 [N] are the observations the policy sees
+    first (after ``reset()``, normalised when ``norm`` is given) and ones after a reset, or what the
+    previous call returned; neither is written.  ``eps_out`` (float32 [n_steps, N, act_dim], optional)
+    receives the noise of every step.  The buffer is reset first.  Returns the next ``(obs,
+    episode_start)``."""
+    import torch
+    N, T, dev = buffer.n_lanes, buffer.n_steps, buffer.device
+    O, A = policy.obs_dim, policy.act_dim
+    f32, u8 = torch.float32, torch.uint8
+    _check("obs", obs, dev, f32, (N, O))
+    _check("episode_start", episode_start, dev, u8, (N,))
+    if eps_out is not None:
+        _check("eps_out", eps_out, dev, f32, (T, N, A))
+    if tuple(buffer.obs_shape) != (O,) or buffer.act_dim != A:
+        raise ValueError(f"collect_rollouts: the buffer holds obs {buffer.obs_shape} / {buffer.act_dim} actions, "
+                         f"the policy takes ({O},) / {A}")
+    z = lambda *s, dt=f32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
+    raw, rew, done, trunc, term = z(N, O), z(N), z(N, dt=u8), z(N, dt=u8), z(N, O)
+    nobs, nrew, nterm = (z(N, O), z(N), z(N, O)) if norm is not None else (raw, rew, term)
+    clipped, tvals = z(N, A), z(N)
+    obs, episode_start = obs.clone(), episode_start.clone()
+    buffer.reset()
+    for t in range(T):
+        # the row's actions, values and log-probs are written in place
+        out = (buffer.actions[t], clipped, buffer.values[t], buffer.log_probs[t])
+        policy.act(obs, out=out, eps_out=None if eps_out is None else eps_out[t])
+        env.step_torch(clipped, raw, rew, done, truncated=trunc, terminal_obs=term)
+        if norm is not None:
+            norm.step(raw, rew, done, nobs, nrew, term_obs=term, term_out=nterm)
+        policy.values(nterm, out=tvals)          # entries of lanes that did not truncate are ignored
+        buffer.add(obs, buffer.actions[t], nrew, episode_start, buffer.values[t], buffer.log_probs[t], truncated=trunc,
+                   terminal_value=tvals)
+        obs.copy_(nobs)
+        episode_start.copy_(done)
+    buffer.compute_returns_and_advantage(policy.values(obs), episode_start)
+    return obs, episode_start
+
+
 class DeviceRolloutBuffer:
     """SB3's ``RolloutBuffer`` as preallocated torch tensors on ``device``: ``observations``
     [T, N, *obs_shape] (``obs_dtype``, None = torch.float32; uint8 frame stacks are allowed), ``actions`` [T, N, A],

@@ -296,6 +296,48 @@ int mrp_gae_device(int device, void* hip_stream, int n_steps, int n_lanes,
                    const float* d_last_values, const uint8_t* d_last_dones,
                    double gamma, double gae_lambda, float* d_advantages, float* d_returns);
 
+/* ------------------------------------------------------------------------------------------
+ * Device policy: SB3's ActorCriticPolicy with MlpExtractor (forward pass, diagonal-Gaussian
+ * sampling, log-prob, value, action clipping) for a batch of lanes in one launch.  The rule,
+ * which the kernel matches bit for bit, is gym_puzzles_amd.policy.policy_ref (DESIGN.md "Device
+ * policy"): n_shared trunk layers, then n_pi policy-tower and n_vf value-tower layers, each
+ * Linear + activation, a linear action head (act_dim outputs), a linear value head and a
+ * state-independent log_std[act_dim]; every Linear is a float32 fmaf chain in ascending k from
+ * the bias.  Limits: obs_dim and every width 1..256, act_dim 1..16, n_shared + max(n_pi, n_vf)
+ * <= 4 (all three may be 0).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mrp_policy mrp_policy;
+#define MRP_POLICY_TANH 0
+#define MRP_POLICY_RELU 1
+
+/* widths: n_shared + n_pi + n_vf layer widths (trunk, policy tower, value tower).  MRP_E_ARG for
+ * dims or counts outside the limits (message: mrp_policy_last_error(NULL)). */
+int mrp_policy_create(int device, int obs_dim, int act_dim, int n_shared, int n_pi, int n_vf, const int* widths,
+                      int activation, mrp_policy** out);
+void mrp_policy_destroy(mrp_policy* p);
+const char* mrp_policy_last_error(const mrp_policy* p);
+/* Host pointers in torch's [out][in] layout: weights / biases hold n_shared + n_pi + n_vf + 2
+ * entries (trunk, policy tower, value tower, action head, value head); std[i] is
+ * float32(exp(float64(log_std[i]))), computed by the caller.  Packs the weights for the kernel and
+ * copies them; synchronises the device. */
+int mrp_policy_set_params(mrp_policy* p, const float* const* weights, const float* const* biases, const float* log_std,
+                          const float* std);
+/* One launch on `hip_stream` (NULL = the null stream): d_obs [n_lanes][obs_dim]; noise d_eps_in
+ * [n_lanes][act_dim], or NULL for the device counter RNG keyed by (seed, lane_offset + lane,
+ * counter * act_dim + i) (Box-Muller in float64 rounded to float32); deterministic: action = mean.
+ * Outputs: d_actions [n_lanes][act_dim] (unclipped, what SB3 stores), optional d_clipped (what
+ * steps the env), d_values [n_lanes], d_log_probs [n_lanes] and d_eps_out (the noise used).
+ * MRP_E_ARG: n_lanes < 1, a null d_obs / d_actions, an output equal to an input or to another
+ * output; MRP_E_STATE before mrp_policy_set_params.  Asynchronous. */
+int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, const float* d_eps_in,
+                          uint64_t seed, uint64_t lane_offset, uint64_t counter, int deterministic, float* d_actions,
+                          float* d_clipped, float* d_values, float* d_log_probs, float* d_eps_out);
+/* Trunk + value tower + value head only (V(terminal_obs), last_values): the same bits as
+ * mrp_policy_act_device's d_values. */
+int mrp_policy_values_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, float* d_values);
+/* Device self-test of the policy's tanh rule (mrp_math.h tanh_f32) on n host inputs (host output). */
+int mrp_selftest_tanh(int device, const float* x, float* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

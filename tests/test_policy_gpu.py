@@ -1,0 +1,343 @@
+"""GPU checks of the device policy (csrc/mrp_policy.hip through gym_puzzles_amd.policy.DevicePolicy):
+every output equals the numpy rule policy_ref on bit patterns."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from gym_puzzles_amd import policy as P
+from gym_puzzles_amd.rollout import gae_ref
+
+pytestmark = pytest.mark.gpu
+
+LANES = (1, 31, 33, 65, 130)      # partial tiles, a second workgroup, a partial tile in a later workgroup
+# obs, act, (S, P, V), widths (trunk, policy tower, value tower), activation
+ARCHS = {
+    "sb3-default": (28, 6, (0, 2, 2), [64, 64, 64, 64], "tanh"),
+    "reference-config": (28, 6, (2, 0, 0), [256, 256], "tanh"),
+    "odd-k-wide-head": (27, 15, (1, 1, 1), [40, 24, 8], "relu"),
+    "heads-only": (69, 4, (0, 0, 0), [], "tanh"),
+    "one-by-one": (1, 1, (0, 1, 0), [1], "relu"),
+}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same(got, want, what):
+    got = got.cpu().numpy() if hasattr(got, "cpu") else got
+    bad = np.flatnonzero(_bits(got).ravel() != _bits(want).ravel())
+    assert bad.size == 0, f"{what}: {bad.size} of {want.size} differ, first at {bad[:5]}: {got.ravel()[bad[:5]]} != {want.ravel()[bad[:5]]}"
+
+
+def _params(name, seed=0, negzero_bias=False):
+    obs_dim, act_dim, (S, Pn, V), widths, activation = ARCHS[name]
+    rng = np.random.default_rng(seed)
+
+    def lin(k, n):
+        w = (rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32)
+        b = (rng.standard_normal(n) * 0.3).astype(np.float32)
+        if negzero_bias:        # all weights negative: a row of +0 makes products of -0, which leave a bias of -0 alone
+            w, b = -np.abs(w), np.full(n, -0.0, np.float32)
+        return w, b
+
+    def tower(k, ws):
+        out = []
+        for n in ws:
+            out.append(lin(k, n))
+            k = n
+        return out, k
+    shared, kt = tower(obs_dim, widths[:S])
+    pi, kp = tower(kt, widths[S:S + Pn])
+    vf, kv = tower(kt, widths[S + Pn:])
+    log_std = np.linspace(-0.8, 0.2, act_dim).astype(np.float32)
+    return P.PolicyParams(shared, pi, vf, lin(kp, act_dim), lin(kv, 1), log_std, activation)
+
+
+_CACHE = {}
+
+
+def _case(name):
+    """(params, obs for max(LANES), eps, reference outputs): computed once per architecture, never changed."""
+    if name not in _CACHE:
+        params = _params(name)
+        rng = np.random.default_rng(17)
+        N = max(LANES)
+        obs = rng.standard_normal((N, params.obs_dim)).astype(np.float32)
+        eps = rng.standard_normal((N, params.act_dim)).astype(np.float32)
+        _CACHE[name] = (params, obs, eps, P.policy_ref(params, obs, eps))
+    return _CACHE[name]
+
+
+@pytest.mark.parametrize("name", list(ARCHS))
+def test_bitwise_forward(gpu_lib, name):
+    import torch
+    params, obs, eps, want = _case(name)
+    pol = P.DevicePolicy.from_params(params)
+    for N in LANES:
+        got = pol.act(torch.from_numpy(obs[:N]).cuda(), eps=torch.from_numpy(eps[:N]).cuda())
+        for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
+            _same(g, w[:N], f"{name} N={N} {what}")
+    assert pol.counter == 0, "host-supplied noise leaves the counter alone"
+    pol.close()
+
+
+@pytest.mark.parametrize("name", ["sb3-default", "odd-k-wide-head", "heads-only"])
+def test_zeros_and_negative_zeros(gpu_lib, name):
+    """Observation rows of +0 and of -0 with biases of -0 and negative weights: every layer's products
+    are zeros of one sign, so the outputs are zeros whose sign alternates with the depth, and a pad term
+    fma(0, 0, acc) anywhere in a chain would turn a -0 into +0."""
+    import torch
+    params = _params(name, seed=4, negzero_bias=True)
+    obs = np.random.default_rng(1).standard_normal((40, params.obs_dim)).astype(np.float32)
+    obs[3] = 0.0
+    obs[36] = -0.0
+    eps = np.zeros((40, params.act_dim), np.float32)
+    eps[:, ::2] = -0.0
+    want = P.policy_ref(params, obs, eps)
+    assert (want[0][3] == 0).all() and (want[2][[3, 36]] == 0).all()
+    assert np.signbit(want[0][[3, 36]]).any() or np.signbit(want[2][[3, 36]]).any(), "the case holds negative zeros"
+    pol = P.DevicePolicy.from_params(params)
+    got = pol.act(torch.from_numpy(obs).cuda(), eps=torch.from_numpy(eps).cuda())
+    for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
+        _same(g, w, f"{name} {what}")
+    pol.close()
+
+
+@pytest.mark.parametrize("name", ["sb3-default", "reference-config", "odd-k-wide-head"])
+def test_values_only_and_deterministic(gpu_lib, name):
+    import torch
+    params, obs, eps, want = _case(name)
+    pol = P.DevicePolicy.from_params(params)
+    d_obs = torch.from_numpy(obs).cuda()
+    a, c, v, lp = pol.act(d_obs, eps=torch.from_numpy(eps).cuda())
+    _same(pol.values(d_obs), v.cpu().numpy(), "values() against act's values")
+    _same(pol.values(d_obs[:33].contiguous()), want[2][:33], "values() against the rule")
+    det = pol.act(d_obs, deterministic=True)
+    wdet = P.policy_ref(params, obs, deterministic=True)
+    for g, w, what in zip(det, wdet, ("actions", "clipped", "values", "log_probs")):
+        _same(g, w, f"deterministic {what}")
+    mean = P.linear_ref(P.features_ref(params, obs, "pi"), *params.action)
+    _same(det[0], mean, "deterministic actions are the mean")
+    assert pol.counter == 0
+    pol.close()
+
+
+def _tanh_inputs():
+    rng = np.random.default_rng(9)
+    sweep = np.linspace(-22, 22, 100_001).astype(np.float32)
+    rand = rng.integers(0, 1 << 32, 100_000, dtype=np.uint64).astype(np.uint32).view(np.float32)
+    special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e-45, -1e-45, 1.1754944e-38, 20.0, -20.0], np.float32)
+    special = np.concatenate([special, np.array([0x7F800001, 0xFFC00123, 0x007FFFFF, 0x807FFFFF], np.uint32).view(np.float32)])
+    near = []
+    for x in P.TANH_BRANCH_POINTS:
+        b = int(np.float32(x).view(np.uint32))
+        near.append(np.arange(b - 2000, b + 2001, dtype=np.uint32).view(np.float32))
+    near = np.concatenate(near)
+    return np.concatenate([sweep, rand, special, near, -near])
+
+
+def test_tanh_on_the_device(gpu_lib):
+    from gym_puzzles_amd import _native
+    x = _tanh_inputs()
+    assert x.size >= 500_000 and np.isnan(x).any() and np.isinf(x).any()
+    out = np.zeros_like(x)
+    rc = gpu_lib.mrp_selftest_tanh(0, _native._p(x), _native._p(out), x.size)
+    assert rc == 0
+    _same(out, P.tanh_ref(x), "tanh_f32 on the device against tanh_ref")
+
+
+def test_device_rng(gpu_lib):
+    import torch
+    params = _params("odd-k-wide-head", seed=2)
+    N, A = 256, params.act_dim
+    obs = np.random.default_rng(3).standard_normal((N, params.obs_dim)).astype(np.float32)
+    d_obs = torch.from_numpy(obs).cuda()
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device="cuda")  # noqa: E731
+    pol = P.DevicePolicy.from_params(params, seed=1234)
+    e0 = z(N, A)
+    out0 = [t.cpu().numpy() for t in pol.act(d_obs, eps_out=e0)]
+    assert pol.counter == 1
+    # the outputs are the rule applied to the emitted noise
+    for g, w, what in zip(out0, P.policy_ref(params, obs, e0.cpu().numpy()), ("actions", "clipped", "values", "log_probs")):
+        _same(g, w, f"device noise: {what}")
+    # lanes are keyed by lane_offset + lane: two half batches make the whole
+    halves = []
+    for off in (0, N // 2):
+        half = P.DevicePolicy.from_params(params, seed=1234, lane_offset=off)
+        eh = z(N // 2, A)
+        oh = half.act(d_obs[off:off + N // 2].contiguous(), eps_out=eh)
+        halves.append([t.cpu().numpy() for t in oh] + [eh.cpu().numpy()])
+        half.close()
+    for i, what in enumerate(("actions", "clipped", "values", "log_probs", "eps")):
+        whole = out0[i] if i < 4 else e0.cpu().numpy()
+        _same(np.concatenate([halves[0][i], halves[1][i]]), whole, f"half batches: {what}")
+    # the same counter repeats, the next one differs
+    pol.counter = 0
+    e0b = z(N, A)
+    pol.act(d_obs, eps_out=e0b)
+    _same(e0b, e0.cpu().numpy(), "the same counter")
+    e1 = z(N, A)
+    pol.act(d_obs, eps_out=e1)
+    assert pol.counter == 2 and not np.array_equal(e1.cpu().numpy(), e0.cpu().numpy())
+    other = P.DevicePolicy.from_params(params, seed=1235)
+    es = z(N, A)
+    other.act(d_obs, eps_out=es)
+    assert not np.array_equal(es.cpu().numpy(), e0.cpu().numpy()), "the seed keys the noise"
+    other.close()
+    # statistics over 256 lanes x 15 dims x 64 counters: six-sigma bounds under the normal law
+    pol.counter = 0
+    all_eps = z(64, N, A)
+    for c in range(64):
+        pol.act(d_obs, eps_out=all_eps[c])
+    e = all_eps.cpu().numpy().astype(np.float64).ravel()
+    n = e.size
+    assert n == 256 * 15 * 64 and np.isfinite(e).all()
+    tail = (np.abs(e) > 1.96).mean()
+    print(f"eps: mean {e.mean():.5f} var {e.var():.5f} tail {tail:.5f} n {n}")
+    assert abs(e.mean()) <= 6 / np.sqrt(n)
+    assert abs(e.var() - 1) <= 6 * np.sqrt(2 / n)
+    assert abs(tail - 0.05) <= 6 * np.sqrt(0.05 * 0.95 / n)
+    lanes_differ = np.unique(all_eps[0].cpu().numpy(), axis=0).shape[0]
+    assert lanes_differ == N, "every lane draws its own noise"
+    pol.close()
+
+
+def test_inputs_are_not_written_and_outputs_are_the_callers(gpu_lib):
+    import torch
+    params, obs, eps, want = _case("sb3-default")
+    N = 65
+    pol = P.DevicePolicy.from_params(params)
+    d_obs, d_eps = torch.from_numpy(obs[:N]).cuda(), torch.from_numpy(eps[:N]).cuda()
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device="cuda")  # noqa: E731
+    out = (z(N, 6), z(N, 6), z(N), z(N))
+    got = pol.act(d_obs, eps=d_eps, out=out)
+    assert all(g is o for g, o in zip(got, out))
+    vout = z(N)
+    assert pol.values(d_obs, out=vout) is vout
+    _same(d_obs, obs[:N], "obs after the launches")
+    _same(d_eps, eps[:N], "eps after the launches")
+    _same(out[3], want[3][:N], "log_probs")
+    _same(vout, want[2][:N], "values")
+    pol.close()
+
+
+def test_argument_errors(gpu_lib):
+    import torch
+    params, obs, eps, _ = _case("sb3-default")
+    N = 8
+    pol = P.DevicePolicy.from_params(params)
+    d_obs, d_eps = torch.from_numpy(obs[:N]).cuda(), torch.from_numpy(eps[:N]).cuda()
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device="cuda")  # noqa: E731
+    good = lambda: [z(N, 6), z(N, 6), z(N), z(N)]  # noqa: E731
+    bad_calls = [
+        lambda: pol.act(d_obs.cpu()),                                            # wrong device
+        lambda: pol.act(d_obs.double()),                                         # dtype
+        lambda: pol.act(z(N, 27)),                                               # shape
+        lambda: pol.act(z(N, 56)[:, ::2]),                                       # non-contiguous
+        lambda: pol.act(d_obs, eps=z(N, 5)),
+        lambda: pol.act(d_obs, eps=d_eps.cpu()),
+        lambda: pol.act(d_obs, out=(z(N, 6), z(N, 6), z(N))),
+        lambda: pol.act(d_obs, out=good()[:3] + [z(N, dt=torch.float64)]),
+        lambda: pol.act(d_obs, out=good()[:2] + [z(N + 1), z(N)]),
+        lambda: pol.act(d_obs, eps=d_eps, out=[d_eps] + good()[1:]),             # an output aliases an input
+        lambda: pol.act(z(N, 28), out=(lambda t: [t, t, z(N), z(N)])(z(N, 6))),  # two outputs alias
+        lambda: pol.act(d_obs, eps_out=z(N, 7)),
+        lambda: pol.values(d_obs, out=z(N + 1)),
+        lambda: pol.values(d_obs.cpu()),
+        lambda: pol.values(z(0, 28)),
+    ]
+    for call in bad_calls:
+        with pytest.raises(ValueError):
+            call()
+    with pytest.raises(ValueError):
+        pol.values(z(N, 1).expand(N, 28))                                        # stride-0 rows
+    empty = P.DevicePolicy(28, 6, 0, 2, 2, [64, 64, 64, 64])
+    with pytest.raises(ValueError, match="set_params"):
+        empty.act(d_obs)
+    with pytest.raises(ValueError, match="set_params"):
+        empty.values(d_obs)
+    with pytest.raises(ValueError):
+        empty.set_params(_case("reference-config")[0])
+    empty.set_params(params)
+    _same(empty.values(d_obs), _case("sb3-default")[3][2][:N], "values after set_params")
+    with pytest.raises(ValueError):
+        P.DevicePolicy(28, 17, 0, 0, 0, [])
+    with pytest.raises(ValueError):
+        P.DevicePolicy(28, 6, 3, 2, 0, [8] * 5)
+    empty.close()
+    pol.close()
+
+
+@pytest.mark.parametrize("with_norm", [False, True])
+def test_collect_rollouts_end_to_end(gpu_lib, with_norm):
+    """collect_rollouts on MultiRobotPuzzle-v0, 64 lanes, 12 steps, a 5-step TimeLimit, the default
+    architecture: every buffer row is the rule on the host copy of that row, the env was stepped with
+    the clipped actions (a second env replays them), and the advantages are gae_ref on the host copies."""
+    import torch
+    from gym_puzzles_amd import DeviceRolloutBuffer, DeviceVecNormalize, MultiRobotPuzzleVecEnv
+    from gym_puzzles_amd.rollout import collect_rollouts
+    N, T = 64, 12
+    dev = torch.device("cuda", 0)
+    env = MultiRobotPuzzleVecEnv("MultiRobotPuzzle-v0", N, seed=3, max_episode_steps=5)
+    O, A = env.observation_space.shape[0], env.action_space.shape[0]
+    params = _params("sb3-default", seed=6)
+    assert (params.obs_dim, params.act_dim) == (O, A)
+    pol = P.DevicePolicy.from_params(params, seed=77)
+    buf = DeviceRolloutBuffer(T, N, (O,), A, device=0, gamma=0.99, gae_lambda=0.95)
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
+    raw0 = torch.from_numpy(env.reset()).to(dev)
+    norm = DeviceVecNormalize(N, O, device=0) if with_norm else None
+    obs0 = raw0
+    if norm is not None:
+        obs0 = z(N, O)
+        norm.reset(raw0, obs0)
+    start0 = torch.ones(N, dtype=torch.uint8, device=dev)
+    eps = z(T, N, A)
+    obs_in, start_in = obs0.clone(), start0.clone()
+    nxt_obs, nxt_start = collect_rollouts(env, pol, buf, obs0, start0, norm=norm, eps_out=eps)
+    assert buf.full and pol.counter == T
+    _same(obs0, obs_in.cpu().numpy(), "the caller's obs")
+    assert torch.equal(start0, start_in)
+    h = lambda t: t.cpu().numpy()  # noqa: E731
+    b_obs, b_act, b_val, b_lp, h_eps = h(buf.observations), h(buf.actions), h(buf.values), h(buf.log_probs), h(eps)
+    # replay: a second env with the same seed, stepped with the clipped stored actions
+    env2 = MultiRobotPuzzleVecEnv("MultiRobotPuzzle-v0", N, seed=3, max_episode_steps=5)
+    raw = torch.from_numpy(env2.reset()).to(dev)
+    norm2 = DeviceVecNormalize(N, O, device=0) if with_norm else None
+    cur = raw
+    if norm2 is not None:
+        cur = z(N, O)
+        norm2.reset(raw, cur)
+    nraw, rew, done, trunc, term = z(N, O), z(N), z(N, dt=torch.uint8), z(N, dt=torch.uint8), z(N, O)
+    nobs, nrew, nterm = (z(N, O), z(N), z(N, O)) if with_norm else (nraw, rew, term)
+    assert (np.abs(b_act) > 1).any(), "some stored actions lie outside the box, so clipping is visible"
+    n_trunc = 0
+    for t in range(T):
+        _same(cur, b_obs[t], f"row {t}: the replayed env's observations (it was stepped with the clipped actions)")
+        want = P.policy_ref(params, b_obs[t], h_eps[t])
+        _same(b_act[t], want[0], f"row {t}: the stored actions are the unclipped ones")
+        _same(b_val[t], want[2], f"row {t}: values")
+        _same(b_lp[t], want[3], f"row {t}: log_probs")
+        env2.step_torch(torch.from_numpy(want[1]).to(dev), nraw, rew, done, truncated=trunc, terminal_obs=term)
+        if norm2 is not None:
+            norm2.step(nraw, rew, done, nobs, nrew, term_obs=term, term_out=nterm)
+        _same(buf.rewards[t], h(nrew), f"row {t}: rewards")
+        _same(buf.truncated[t].to(torch.float32), h(trunc).astype(np.float32), f"row {t}: truncated")
+        m = h(trunc).astype(bool)
+        if m.any():
+            n_trunc += int(m.sum())
+            _same(h(buf.terminal_values[t])[m], P.values_ref(params, h(nterm)[m]), f"row {t}: terminal values")
+        cur = nobs.clone()
+    assert n_trunc >= 64
+    _same(nxt_obs, h(cur), "the returned observations")
+    assert torch.equal(nxt_start, done)
+    last_values = P.values_ref(params, h(cur))
+    want_a, want_r = gae_ref(h(buf.rewards), b_val, h(buf.episode_starts).astype(np.float32), last_values, h(done), 0.99, 0.95,
+                             h(buf.truncated), h(buf.terminal_values))
+    _same(buf.advantages, want_a, "advantages")
+    _same(buf.returns, want_r, "returns")
+    assert h(buf.episode_starts)[0].all()
+    for x in (env, env2, pol) + ((norm, norm2) if with_norm else ()):
+        x.close()
