@@ -13,9 +13,13 @@ gym_puzzles env interface.  See DESIGN.md.
     DevicePolicy           SB3 ActorCriticPolicy (MlpExtractor) on the device: forward, sampling, log-prob, value
                            and clipping in one launch (policy.policy_ref / tanh_ref state the rule in numpy);
                            rollout.collect_rollouts runs act / step / normalise / add without a host sync
+    DevicePPO              one optimiser step of SB3's PPO.train() on the device -- evaluate_actions, losses,
+                           backward, grad-norm clip, Adam -- writing the DevicePolicy's parameters in place
+                           (ppo.ppo_grad_ref / adam_ref / ppo_train_ref / exp_ref state the rule in numpy)
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
 from .policy import policy_ref, tanh_ref  # noqa: F401  (pure numpy)
+from .ppo import adam_ref, exp_ref, ppo_grad_ref, ppo_train_ref  # noqa: F401  (pure numpy)
 
 
 def __getattr__(name):
@@ -33,6 +37,9 @@ def __getattr__(name):
     if name == "DevicePolicy":
         from . import policy
         return policy.DevicePolicy
+    if name == "DevicePPO":
+        from . import ppo
+        return ppo.DevicePPO
     if name == "collect_rollouts":
         from . import rollout
         return rollout.collect_rollouts

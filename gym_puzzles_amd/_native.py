@@ -24,7 +24,7 @@ COUNTER_NAMES = ("steps", "resets", "toi_events", "position_iterations", "touchi
 
 MAXF = 24   # csrc/mrp_config.h: fixtures per env (mrp_shapes fills MAXF rows)
 
-_i, _d, _u64, _P = ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p
+_i, _d, _u64, _P, _f = ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_float
 _ip, _PP = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)
 # The C ABI of include/mrp.h, stated once: name -> (restype, argtypes).  load() applies it, EXPORTED is
 # its key list, and tests/test_abi.py compares that list with the header and with the library's exports.
@@ -96,6 +96,15 @@ ABI = {
     "mrp_policy_act_device": (_i, [_P, _P, _i, _P, _P, _u64, _u64, _u64, _i] + [_P] * 5),
     "mrp_policy_values_device": (_i, [_P, _P, _i, _P, _P]),
     "mrp_selftest_tanh": (_i, [_i, _P, _P, _i]),
+    "mrp_policy_get_params": (_i, [_P, _PP, _PP, _P, _P]),
+    "mrp_ppo_create": (_i, [_P, _i, _PP]),
+    "mrp_ppo_destroy": (None, [_P]),
+    "mrp_ppo_last_error": (ctypes.c_char_p, [_P]),
+    "mrp_ppo_n_params": (_i, [_P]),
+    "mrp_ppo_grad_device": (_i, [_P, _P, _i] + [_P] * 5 + [_f, _f, _d, _P, _P]),
+    "mrp_ppo_step_device": (_i, [_P, _P, _i] + [_P] * 5 + [_f, _f, _d, _d] + [_f] * 7 + [_P]),
+    "mrp_ppo_get_state": (_i, [_P, _P, _P]),
+    "mrp_selftest_exp": (_i, [_i, _P, _P, _i]),
 }
 EXPORTED = tuple(ABI)
 

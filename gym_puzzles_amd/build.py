@@ -28,9 +28,11 @@ SOURCES = ([(f, f + ".o", None) for f in ("mrp_kernels.hip", "mrp_tables.cpp", "
 # in a list of its own: SOURCES is "the three shared units plus one object per env id" wherever the
 # registry is checked or an A/B library picks its units.
 POLICY_SOURCES = [("mrp_policy.hip", "mrp_policy.hip.o", None)]
-UNITS = SOURCES + POLICY_SOURCES
+# The PPO update's unit (csrc/mrp_ppo.hip): it shares csrc/mrp_policy_net.h with the policy's unit.
+PPO_SOURCES = [("mrp_ppo.hip", "mrp_ppo.hip.o", None)]
+UNITS = SOURCES + POLICY_SOURCES + PPO_SOURCES
 HEADERS = ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h", "mrp_ops.h", "mrp_lane.h", "mrp_render.h",
-           "mrp_pixels.h", "mrp_microbench.h")
+           "mrp_pixels.h", "mrp_microbench.h", "mrp_policy_net.h")
 
 
 def deps(csrc: str = CSRC) -> list[str]:

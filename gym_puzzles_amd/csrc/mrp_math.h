@@ -326,6 +326,32 @@ MRP_HD float tanh_f32(float x) {
 }
 
 // ---------------------------------------------------------------------------------------
+// exp for the PPO update's probability ratio and for std = exp(log_std) after an optimiser step:
+// built like tanh_f32 and restated operation for operation by gym_puzzles_amd.ppo.exp_ref.
+//   y = x clamped to [-104, 89], n = nearest integer to y / ln 2 (ties away), the same two-part ln 2
+//   reduction and degree-11 Taylor expm1, E = 2^n (1 + p) in float64, one rounding to float32.
+// That rounding takes exp(89) and above to +inf and goes through the subnormals to +0 (exp(-104) lies
+// below half the least subnormal); NaN comes back unchanged.  Error against the real exp: 0.5 ulp +
+// 2^-25 (the float64 evaluation error, orders below a float32 ulp).
+// ---------------------------------------------------------------------------------------
+MRP_HD float exp_f32(float x) {
+    const bool nan = (f2u(x) & 0x7fffffffu) > 0x7f800000u;
+    double y = (double)(nan ? 0.0f : x);
+    y = y < -104.0 ? -104.0 : y;
+    y = y > 89.0 ? 89.0 : y;
+    const double t = y * TH_INV_LN2;
+    const int n = (int)(t + (t < 0.0 ? -0.5 : 0.5));
+    const double dn = (double)n;
+    const double r = (y - dn * TH_LN2_HI) - dn * TH_LN2_LO;
+    double q = TH_C11;
+    q = q * r + TH_C10; q = q * r + TH_C9; q = q * r + TH_C8; q = q * r + TH_C7; q = q * r + TH_C6;
+    q = q * r + TH_C5; q = q * r + TH_C4; q = q * r + TH_C3; q = q * r + TH_C2;
+    const double p = r + (r * r) * q;
+    const float e = (float)(u2d((uint64_t)(1023 + n) << 52) * (1.0 + p));
+    return nan ? x : e;
+}
+
+// ---------------------------------------------------------------------------------------
 // Counter-based RNG for on-device resets and synthetic actions (pure integer SplitMix64
 // mixing; identical on host and device, so the CPU oracle can replay device resets).
 // ---------------------------------------------------------------------------------------

@@ -27,121 +27,11 @@
 
 #include "../../include/mrp.h"
 #include "mrp_math.h"
+#include "mrp_policy_net.h"
+
+using namespace mrp_pol;
 
 namespace {
-
-constexpr int P_NT = 256;        // 4 waves
-constexpr int P_TILE = 32;       // lanes (rows) per workgroup
-constexpr int P_LDA = 258;       // LDS row stride in floats: rows land 2 banks apart, so the A read
-                                 // (32 rows x 2 consecutive k) touches 64 different banks
-constexpr int P_MAXW = 256, P_MAXA = 16, P_MAXL = 4;
-constexpr int P_U = 8;          // k-steps of a hidden layer whose operands are in flight together
-constexpr int P_HS = P_MAXA + 1; // head outputs per row: act_dim means, then the value
-constexpr int STREAM_U1 = 4, STREAM_U2 = 5;   // rng_u01 stream ids (1-3: resets and synthetic actions)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Layer { const float* w; const float* b; int K, N, Npad; };   // w packed [K][Npad], b [Npad]
-struct Head { const float* w; const float* b; int K, Kpad; };        // w [out][Kpad]: torch's rows, padded to 4 floats
-struct Net {
-    int obs_dim, act_dim, n_shared, n_pi, n_vf, relu;
-    Layer shared[P_MAXL], pi[P_MAXL], vf[P_MAXL];
-    Head act, val;
-    const float* log_std; const float* std;
-};
-
-__device__ __forceinline__ float activate(float v, int relu) { return relu ? mrp::fmax_(v, 0.0f) : mrp::tanh_f32(v); }
-
-// dst[32][N] = act(src[32][K] . W + b); src and dst are different LDS buffers
-__device__ __forceinline__ void hidden_layer(const Layer& L, const float* __restrict__ src, float* __restrict__ dst, int relu) {
-    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 31, h = l >> 5;
-    const int K2 = L.K & ~1, ntiles = L.Npad >> 5;
-    const float* ap = src + c * P_LDA + h;                 // A[i = l & 31][k = l >> 5]
-    for (int t = wave; t < ntiles; t += 4) {
-        const int col = t * 32 + c;
-        const float* wp = L.w + (size_t)h * L.Npad + col;  // B[k = l >> 5][j = l & 31]
-        const float bias = L.b[col];
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = bias;
-        // k-steps in chunks of P_U: the next chunk's operands are requested before the chunk in hand
-        // runs, so the L2 latency of a B row hides behind P_U matrix instructions of 64 cycles each
-        const int nchunk = K2 / (2 * P_U);
-        float a0[P_U], b0[P_U], a1[P_U] = {}, b1[P_U] = {};
-        if (nchunk > 0) {
-#pragma unroll
-            for (int u = 0; u < P_U; ++u) { a0[u] = ap[2 * u]; b0[u] = wp[(size_t)(2 * u) * L.Npad]; }
-        }
-        int k = 0;
-        for (int ch = 0; ch < nchunk; ++ch, k += 2 * P_U) {
-            if (ch + 1 < nchunk) {
-#pragma unroll
-                for (int u = 0; u < P_U; ++u) {
-                    a1[u] = ap[k + 2 * (P_U + u)];
-                    b1[u] = wp[(size_t)(k + 2 * (P_U + u)) * L.Npad];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < P_U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc, 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < P_U; ++u) { a0[u] = a1[u]; b0[u] = b1[u]; }
-        }
-        // the last, partial chunk: its loads go out together (an index past the end reads k-step 0 again
-        // and is not used), its matrix instructions run under wave-uniform tests
-#pragma unroll
-        for (int u = 0; u < P_U; ++u) {
-            const int kk = k + 2 * u < K2 ? k + 2 * u : 0;
-            a0[u] = ap[kk]; b0[u] = wp[(size_t)kk * L.Npad];
-        }
-#pragma unroll
-        for (int u = 0; u < P_U; ++u)
-            if (k + 2 * u < K2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], b0[u], acc, 0, 0, 0);
-        // C/D: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-        if (L.K & 1) {
-            const float wv = L.w[(size_t)K2 * L.Npad + col];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                acc[r] = __builtin_fmaf(src[row * P_LDA + K2], wv, acc[r]);
-            }
-        }
-        if (col < L.N) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                dst[row * P_LDA + col] = activate(acc[r], relu);
-            }
-        }
-    }
-}
-
-// out[row][o0 + o] = fmaf chain over src[row][0..K) and row o of w, from b[o]; 32 rows x 8 outputs at a time.
-// The rows of w are padded to Kpad (a multiple of 4) in the device image, so 4 weights come per load.
-__device__ __forceinline__ void head(const Head& H, int n_out, const float* __restrict__ src, float* __restrict__ out, int o0) {
-    const int row = threadIdx.x & 31, nq = H.K >> 2;
-    const float* x = src + row * P_LDA;
-    for (int o = threadIdx.x >> 5; o < n_out; o += P_NT / 32) {
-        const float* w = H.w + (size_t)o * H.Kpad;
-        const float4* w4 = reinterpret_cast<const float4*>(w);
-        float acc = H.b[o];
-        int q = 0;
-        for (; q + P_U <= nq; q += P_U) {
-            float4 wv[P_U];
-#pragma unroll
-            for (int u = 0; u < P_U; ++u) wv[u] = w4[q + u];
-#pragma unroll
-            for (int u = 0; u < P_U; ++u) {
-                const float* xk = x + 4 * (q + u);
-                acc = __builtin_fmaf(xk[0], wv[u].x, acc);
-                acc = __builtin_fmaf(xk[1], wv[u].y, acc);
-                acc = __builtin_fmaf(xk[2], wv[u].z, acc);
-                acc = __builtin_fmaf(xk[3], wv[u].w, acc);
-            }
-        }
-        for (int k = 4 * q; k < H.K; ++k) acc = __builtin_fmaf(x[k], w[k], acc);
-        out[row * P_HS + o0 + o] = acc;
-    }
-}
 
 // a tower of n layers from buffer `in`, writing alternately to buffers a and b; returns the buffer of its output
 __device__ __forceinline__ int tower(const Layer* L, int n, float* lds, int in, int a, int b, int relu) {
@@ -232,24 +122,6 @@ __global__ void k_tanh(const float* __restrict__ x, float* __restrict__ out, int
 thread_local std::string g_policy_create_error;
 
 }  // namespace
-
-struct mrp_policy {
-    int device = 0, ready = 0, n_layers = 0;
-    int widths[3 * P_MAXL] = {};
-    Net net = {};
-    float* d_params = nullptr;
-    size_t n_floats = 0;
-    std::string err;
-};
-
-#define PCHK(p, expr)                                                      \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) {                                            \
-            (p)->err = std::string(#expr) + ": " + hipGetErrorString(_e);  \
-            return MRP_E_HIP;                                              \
-        }                                                                  \
-    } while (0)
 
 namespace {
 
@@ -385,6 +257,45 @@ int mrp_policy_set_params(mrp_policy* p, const float* const* weights, const floa
     PCHK(p, hipDeviceSynchronize());   // no launch still reads the old parameters
     PCHK(p, hipMemcpy(p->d_params, h.data(), p->n_floats * sizeof(float), hipMemcpyHostToDevice));
     p->ready = 1;
+    ++p->version;
+    return MRP_OK;
+}
+
+int mrp_policy_get_params(mrp_policy* p, float* const* weights, float* const* biases, float* log_std, float* std) {
+    if (!p) return MRP_E_ARG;
+    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_get_params: ") + what; return MRP_E_ARG; };
+    if (!weights || !biases || !log_std || !std) return bad("null pointer");
+    for (int i = 0; i < p->n_layers + 2; ++i)
+        if (!weights[i] || !biases[i]) return bad("null layer pointer");
+    if (!p->ready) { p->err = "mrp_policy_get_params: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    const Net& n = p->net;
+    std::vector<float> h(p->n_floats);
+    PCHK(p, hipSetDevice(p->device));
+    PCHK(p, hipDeviceSynchronize());   // every launch that writes the parameters has finished
+    PCHK(p, hipMemcpy(h.data(), p->d_params, p->n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    const float* d0 = p->d_params;
+    auto at = [&](const float* dev) { return h.data() + (dev - d0); };
+    int li = 0;
+    auto unpack = [&](const Layer* L, int count) {
+        for (int i = 0; i < count; ++i, ++li) {
+            const float* w = at(L[i].w);
+            const float* b = at(L[i].b);
+            for (int j = 0; j < L[i].N; ++j) {
+                for (int k = 0; k < L[i].K; ++k) weights[li][(size_t)j * L[i].K + k] = w[(size_t)k * L[i].Npad + j];
+                biases[li][j] = b[j];
+            }
+        }
+    };
+    unpack(n.shared, n.n_shared); unpack(n.pi, n.n_pi); unpack(n.vf, n.n_vf);
+    for (int o = 0; o < n.act_dim; ++o)
+        for (int k = 0; k < n.act.K; ++k) weights[li][(size_t)o * n.act.K + k] = at(n.act.w)[(size_t)o * n.act.Kpad + k];
+    for (int e = 0; e < n.val.K; ++e) weights[li + 1][e] = at(n.val.w)[e];
+    for (int i = 0; i < n.act_dim; ++i) {
+        biases[li][i] = at(n.act.b)[i];
+        log_std[i] = at(n.log_std)[i];
+        std[i] = at(n.std)[i];
+    }
+    biases[li + 1][0] = at(n.val.b)[0];
     return MRP_OK;
 }
 

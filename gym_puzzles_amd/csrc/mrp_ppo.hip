@@ -1,0 +1,654 @@
+// mrp_ppo.hip -- one optimiser step of SB3's PPO.train() on a minibatch, on the device: evaluate_actions,
+// the clipped surrogate / value / entropy losses, the backward pass through the actor-critic network,
+// global grad-norm clipping and Adam, written into the device policy's parameters in place (DESIGN.md
+// "Device PPO update").  The rule, which the kernels match bit for bit, is gym_puzzles_amd/ppo.py's
+// ppo_grad_ref / adam_ref.  Six launches on the caller's stream, no host synchronisation, no atomics:
+// every reduction has a fixed order.
+//
+//   k_ppo_fb      a workgroup of 4 waves takes a tile of 32 samples forward (k_policy's hidden_layer
+//                 and head, each layer's activation saved to the workspace), evaluates the loss terms
+//                 and the upstream gradients, and goes backward: s = delta . W is the same MFMA loop
+//                 with delta as the A operand in LDS and torch's row-major [out][in] image of the
+//                 weights as B (a k-step's two B rows are contiguous), from +0; delta = s * act' is
+//                 saved to the workspace.
+//   k_ppo_wgrad   one wave per (32x32 tile of a weight matrix, chunk of 256 samples): A[i = j][k = n] is
+//                 delta transposed, B[k = n][col = k] the saved input activation, the MFMA's k runs over
+//                 the chunk's samples (an odd last sample is an explicit fmaf); writes chunk partials.
+//   k_ppo_bsum    the bias and log_std chunk partials (plain adds in sample order) and the chunks'
+//                 float64 sums of the five statistics' terms.
+//   k_ppo_reduce  adds the chunk partials in ascending order into the flat gradient.
+//   k_ppo_norm    one workgroup: the float64 sum of squares in 256 interleaved partials, the clip
+//                 factor, and the five statistics.
+//   k_ppo_adam    flat elementwise clip + Adam on the master vectors; writes both device images of the
+//                 parameters (k_policy's [K][Npad] one and the row-major one) and std = exp_f32(log_std).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/mrp.h"
+#include "mrp_math.h"
+#include "mrp_policy_net.h"
+
+using namespace mrp_pol;
+
+namespace {
+
+constexpr int CHUNK = 256;                 // ppo.py CHUNK: samples per partial sum
+constexpr int NL = 3 * P_MAXL;             // hidden layers at most (trunk, policy tower, value tower)
+constexpr int L_ACT = NL, L_VAL = NL + 1;  // the heads' slots in the delta table
+constexpr int HW = 32;                     // row stride of the heads' delta / log_std-term arrays
+constexpr int NSTAT = 5, SW = 8;           // statistics, and the row stride of their per-sample terms
+
+struct PpoNet {
+    Net net;
+    Layer bwd[NL];         // per hidden layer: w = row-major [N][pad32(K)] image, K = outputs, N = inputs
+    float* act[NL];        // saved activations [max_batch][Npad]
+    float* delta[NL + 2];  // saved deltas [max_batch][Npad]; the heads' are [max_batch][HW]
+    float* lsterm;         // [max_batch][HW]: the samples' log_std gradient terms
+    float* sterm;          // [max_batch][SW]: the samples' statistics terms
+};
+
+struct WTile { const float* delta; const float* x; int dstride, xstride, j0, k0, N, K, off; };  // x == nullptr: the observations
+struct BElem { const float* src; int stride, off; };
+
+__device__ __forceinline__ float* buf(float* lds, int i) { return lds + i * (P_TILE * P_LDA); }
+
+// forward through n layers from buffer `in` (as k_policy's tower), saving each activation
+__device__ __forceinline__ int fwd_tower(const PpoNet& pn, const Layer* L, int li, int n, float* lds, int in, int a, int b,
+                                         int base, int B) {
+    for (int i = 0; i < n; ++i) {
+        const int out = (i & 1) ? b : a;
+        hidden_layer(L[i], buf(lds, in), buf(lds, out), pn.net.relu);
+        __syncthreads();
+        const int N = L[i].N, Npad = L[i].Npad;
+        float* g = pn.act[li + i];
+        for (int e = threadIdx.x; e < P_TILE * N; e += P_NT) {
+            const int row = e / N, col = e - row * N;
+            if (base + row < B) g[(size_t)(base + row) * Npad + col] = buf(lds, out)[row * P_LDA + col];
+        }
+        in = out;
+    }
+    return in;
+}
+
+// backward through n layers: buffer `cur` holds s at the tower's output; returns the buffer of s at its
+// input (nothing is computed into the observations: `to_obs` marks a tower whose first layer reads them)
+__device__ __forceinline__ int bwd_tower(const PpoNet& pn, const Layer* L, int li, int n, float* lds, int cur, int other,
+                                         int to_obs, int base, int B) {
+    const int relu = pn.net.relu;
+    for (int i = n - 1; i >= 0; --i) {
+        const int N = L[i].N, Npad = L[i].Npad;
+        const float* t = pn.act[li + i];
+        float* d = pn.delta[li + i];
+        float* s = buf(lds, cur);
+        for (int e = threadIdx.x; e < P_TILE * N; e += P_NT) {
+            const int row = e / N, col = e - row * N;
+            const bool live = base + row < B;
+            const size_t g = (size_t)(base + row) * Npad + col;
+            const float tv = live ? t[g] : 0.0f;
+            const float dp = relu ? (tv > 0.0f ? 1.0f : 0.0f) : __builtin_fmaf(-tv, tv, 1.0f);
+            const float dl = s[row * P_LDA + col] * dp;
+            s[row * P_LDA + col] = dl;
+            if (live) d[g] = dl;
+        }
+        __syncthreads();
+        if (i == 0 && to_obs) break;
+        hidden_layer<true>(pn.bwd[li + i], s, buf(lds, other), relu);
+        __syncthreads();
+        const int tmp = cur; cur = other; other = tmp;
+    }
+    return cur;
+}
+
+__global__ __launch_bounds__(P_NT) void k_ppo_fb(const PpoNet pn, int B, const float* __restrict__ obs,
+                                                 const float* __restrict__ actions, const float* __restrict__ old_lp,
+                                                 const float* __restrict__ adv_in, const float* __restrict__ ret_in, float clip,
+                                                 float vf2, float invB) {
+    __shared__ float lds[3 * P_TILE * P_LDA];
+    __shared__ float hs[P_TILE * P_HS];     // the heads' outputs, then the log-prob terms, then the heads' deltas
+    __shared__ float gs[P_TILE];
+    const Net& net = pn.net;
+    const int tid = threadIdx.x, base = blockIdx.x * P_TILE;
+    const int D = net.obs_dim, A = net.act_dim, relu = net.relu;
+    const int S = net.n_shared, NP = net.n_pi, NV = net.n_vf;
+    for (int e = tid; e < P_TILE * D; e += P_NT) {
+        const int row = e / D, k = e - row * D;
+        lds[row * P_LDA + k] = base + row < B ? obs[(size_t)(base + row) * D + k] : 0.0f;
+    }
+    __syncthreads();
+    // ---- forward, as k_policy
+    const int T = fwd_tower(pn, net.shared, 0, S, lds, 0, 1, 0, base, B);
+    const int po = fwd_tower(pn, net.pi, S, NP, lds, T, 1 - T, 2, base, B);
+    head(net.act, A, buf(lds, po), hs, 0);
+    __syncthreads();
+    const int vo = fwd_tower(pn, net.vf, S + NP, NV, lds, T, 1 - T, 2, base, B);
+    head(net.val, 1, buf(lds, vo), hs, P_MAXA);
+    __syncthreads();
+    // ---- evaluate: d, the log-prob terms
+    const int row = tid & 31, n = base + row;
+    const bool live = n < B;
+    constexpr int NS = (P_MAXA + 7) / 8;
+    float term[NS], dd[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int i = (tid >> 5) + 8 * s;
+        term[s] = 0.0f; dd[s] = 0.0f;
+        if (i < A && live) {
+            const float m = hs[row * P_HS + i], sd = net.std[i];
+            const float d = actions[(size_t)n * A + i] - m;
+            dd[s] = d;
+            const float q = (-(d * d)) / (2.0f * (sd * sd));
+            term[s] = (q - net.log_std[i]) - 0x1.d67f1cp-1f;   // float32(log(sqrt(2 pi)))
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int i = (tid >> 5) + 8 * s;
+        if (i < A) hs[row * P_HS + i] = term[s];
+    }
+    __syncthreads();
+    // ---- the loss terms and the upstream gradients of a sample
+    if (tid < P_TILE) {
+        float g = 0.0f, dv = 0.0f;
+        if (live) {
+            float lp = 0.0f;
+            for (int i = 0; i < A; ++i) lp = lp + hs[row * P_HS + i];
+            float ent = 0.0f;
+            for (int i = 0; i < A; ++i) ent = ent + ((0.5f + 0x1.d67f1cp-1f) + net.log_std[i]);
+            const float v = hs[row * P_HS + P_MAXA], adv = adv_in[n], ret = ret_in[n];
+            const float diff = lp - old_lp[n];
+            const float ratio = mrp::exp_f32(diff);
+            const float lo = 1.0f - clip, hi = 1.0f + clip;
+            const float pl1 = adv * ratio, pl2 = adv * mrp::fmin_(mrp::fmax_(ratio, lo), hi);
+            const bool first = pl1 <= pl2;
+            g = first ? (-(adv * ratio)) * invB : 0.0f;
+            dv = ((v - ret) * vf2) * invB;
+            const float r1 = ratio - 1.0f;
+            float* st = pn.sterm + (size_t)n * SW;
+            st[0] = -(first ? pl1 : pl2);
+            st[1] = (ret - v) * (ret - v);
+            st[2] = -ent;
+            st[3] = r1 - diff;
+            st[4] = __builtin_fabsf(r1) > clip ? 1.0f : 0.0f;
+            pn.delta[L_VAL][(size_t)n * HW] = dv;
+        }
+        gs[row] = g;
+        hs[row * P_HS + P_MAXA] = dv;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int i = (tid >> 5) + 8 * s;
+        if (i < A) {
+            const float sd = net.std[i], var = sd * sd, g = gs[row], d = dd[s];
+            const float dm = g * (d / var);
+            hs[row * P_HS + i] = dm;
+            if (live) {
+                pn.delta[L_ACT][(size_t)n * HW + i] = dm;
+                pn.lsterm[(size_t)n * HW + i] = g * ((d * d) / var - 1.0f);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- backward.  Every activation is in the workspace, so the three LDS buffers are free.
+    // policy tower: s at the action head's input, a chain over the head's outputs from +0
+    {
+        const int K = net.act.K;
+        float* s = buf(lds, 0);
+        for (int e = tid; e < P_TILE * K; e += P_NT) {
+            const int k = e >> 5;
+            float acc = 0.0f;
+            for (int i = 0; i < A; ++i) acc = __builtin_fmaf(hs[row * P_HS + i], net.act.w[(size_t)i * net.act.Kpad + k], acc);
+            s[row * P_LDA + k] = acc;
+        }
+    }
+    __syncthreads();
+    const int rp = bwd_tower(pn, net.pi, S, NP, lds, 0, 1, S == 0, base, B);
+    // value tower in the two buffers that do not hold the policy tower's s
+    const int x = rp == 0 ? 1 : 0, y = 3 - rp - x;
+    {
+        const int K = net.val.K;
+        float* s = buf(lds, x);
+        const float dv = hs[row * P_HS + P_MAXA];
+        for (int e = tid; e < P_TILE * K; e += P_NT) {
+            const int k = e >> 5;
+            s[row * P_LDA + k] = dv * net.val.w[k];
+        }
+    }
+    __syncthreads();
+    const int rv = bwd_tower(pn, net.vf, S + NP, NV, lds, x, y, S == 0, base, B);
+    if (S > 0) {
+        const int K = net.shared[S - 1].N;
+        float* sv = buf(lds, rv);
+        const float* sp = buf(lds, rp);
+        for (int e = tid; e < P_TILE * K; e += P_NT) {
+            const int k = e >> 5;
+            sv[row * P_LDA + k] = sp[row * P_LDA + k] + sv[row * P_LDA + k];
+        }
+        __syncthreads();
+        (void)bwd_tower(pn, net.shared, 0, S, lds, rv, rp, 1, base, B);
+    }
+}
+
+// one wave per (tile, chunk): partial[chunk][off + j * K + k] = fmaf chain over the chunk's samples n of
+// fma(delta[n][j], x[n][k], acc) from +0
+__global__ __launch_bounds__(P_NT) void k_ppo_wgrad(const WTile* __restrict__ tiles, int n_tiles, int B,
+                                                    const float* __restrict__ obs, int obs_dim, float* __restrict__ partial,
+                                                    int n_params) {
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 31, h = l >> 5;
+    const int n_chunks = (B + CHUNK - 1) / CHUNK;
+    const int gid = blockIdx.x * (P_NT / 64) + wave;
+    if (gid >= n_tiles * n_chunks) return;
+    const int chunk = gid / n_tiles;
+    const WTile t = tiles[gid - chunk * n_tiles];
+    const float* xs = t.x ? t.x : obs;
+    const int xstride = t.x ? t.xstride : obs_dim;
+    const int n0 = chunk * CHUNK, cnt = (B - n0 < CHUNK ? B - n0 : CHUNK), cnt2 = cnt & ~1;
+    const int j = t.j0 + c, k = t.k0 + c;
+    const bool jok = j < t.N, kok = k < t.K;
+    // A[i = l & 31][k = l >> 5] = delta[n + h][j0 + c];  B[k = l >> 5][col = l & 31] = x[n + h][k0 + c]
+    const float* ap = t.delta + (size_t)(n0 + h) * t.dstride + (jok ? j : 0);
+    const float* bp = xs + (size_t)(n0 + h) * xstride + (kok ? k : 0);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    int s = 0;
+    for (; s + 2 * P_U <= cnt2; s += 2 * P_U) {
+        float a[P_U], b[P_U];
+#pragma unroll
+        for (int u = 0; u < P_U; ++u) {
+            a[u] = ap[(size_t)(s + 2 * u) * t.dstride];
+            b[u] = bp[(size_t)(s + 2 * u) * xstride];
+        }
+#pragma unroll
+        for (int u = 0; u < P_U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(jok ? a[u] : 0.0f, kok ? b[u] : 0.0f, acc, 0, 0, 0);
+    }
+    for (; s < cnt2; s += 2) {
+        const float a = ap[(size_t)s * t.dstride], b = bp[(size_t)s * xstride];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(jok ? a : 0.0f, kok ? b : 0.0f, acc, 0, 0, 0);
+    }
+    // C/D: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+    if (cnt & 1) {   // an odd last sample: a zero pad k-step would turn an accumulator of -0 into +0
+        const int nl = n0 + cnt2;
+        const float xv = kok ? xs[(size_t)nl * xstride + k] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int jr = t.j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float dv = jr < t.N ? t.delta[(size_t)nl * t.dstride + jr] : 0.0f;
+            acc[r] = __builtin_fmaf(dv, xv, acc[r]);
+        }
+    }
+    if (kok) {
+        float* out = partial + (size_t)chunk * n_params + t.off;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int jr = t.j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (jr < t.N) out[(size_t)jr * t.K + k] = acc[r];
+        }
+    }
+}
+
+// grid (chunks, blocks over the bias elements + 1): plain adds in sample order from +0; the last block row
+// sums the chunk's statistics terms in float64
+__global__ __launch_bounds__(P_NT) void k_ppo_bsum(const BElem* __restrict__ elems, int n_elems, int B,
+                                                   const float* __restrict__ sterm, float* __restrict__ partial, int n_params,
+                                                   double* __restrict__ spart) {
+    const int chunk = blockIdx.x, n0 = chunk * CHUNK, n1 = (B < n0 + CHUNK ? B : n0 + CHUNK);
+    if (blockIdx.y == gridDim.y - 1) {
+        if (threadIdx.x < NSTAT) {
+            double acc = 0.0;
+            for (int n = n0; n < n1; ++n) acc = acc + (double)sterm[(size_t)n * SW + threadIdx.x];
+            spart[chunk * NSTAT + threadIdx.x] = acc;
+        }
+        return;
+    }
+    const int e = blockIdx.y * P_NT + threadIdx.x;
+    if (e >= n_elems) return;
+    const BElem el = elems[e];
+    float acc = 0.0f;
+    for (int n = n0; n < n1; ++n) acc = acc + el.src[(size_t)n * el.stride];
+    partial[(size_t)chunk * n_params + el.off] = acc;
+}
+
+__global__ __launch_bounds__(P_NT) void k_ppo_reduce(const float* __restrict__ partial, int n_params, int n_chunks, int act_dim,
+                                                     float ent_coef, float* __restrict__ grad) {
+    const int e = blockIdx.x * P_NT + threadIdx.x;
+    if (e >= n_params) return;
+    float g = partial[e];
+    for (int c = 1; c < n_chunks; ++c) g = g + partial[(size_t)c * n_params + e];
+    if (e < act_dim) g = g + (-ent_coef);
+    grad[e] = g;
+}
+
+__global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ grad, int n_params, double max_norm,
+                                                   const double* __restrict__ spart, int n_chunks, int B,
+                                                   float* __restrict__ coef, float* __restrict__ stats) {
+    __shared__ double part[P_NT];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (int e = t; e < n_params; e += P_NT) {
+        const double g = (double)grad[e];
+        acc = acc + g * g;
+    }
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < P_NT; ++i) sum = sum + part[i];
+        const double q = max_norm / (sqrt(sum) + 1e-6);
+        coef[0] = (float)(q < 1.0 ? q : 1.0);
+    } else if (t <= NSTAT) {
+        double sum = 0.0;
+        for (int c = 0; c < n_chunks; ++c) sum = sum + spart[c * NSTAT + (t - 1)];
+        stats[t - 1] = (float)(sum * (1.0 / (double)B));
+    }
+}
+
+struct AdamK { float b1, omb1, b2, omb2, sqrt_bc2, step, eps; };
+
+// the two device images of a parameter: `fwd` indexes the policy's image (k_policy's layout), `row` the
+// row-major image of the hidden weights (-1: none)
+__global__ __launch_bounds__(P_NT) void k_ppo_adam(int n_params, int act_dim, const float* __restrict__ grad,
+                                                   const float* __restrict__ coef, float* __restrict__ param,
+                                                   float* __restrict__ m, float* __restrict__ v, const int* __restrict__ fwd,
+                                                   const int* __restrict__ row, float* __restrict__ image,
+                                                   float* __restrict__ rows, float* __restrict__ std, AdamK k) {
+    const int e = blockIdx.x * P_NT + threadIdx.x;
+    if (e >= n_params) return;
+    const float g = grad[e] * coef[0];
+    const float mn = (k.b1 * m[e]) + (k.omb1 * g);
+    const float vn = (k.b2 * v[e]) + ((k.omb2 * g) * g);
+    const float denom = (sqrtf(vn) / k.sqrt_bc2) + k.eps;
+    const float p = param[e] - k.step * (mn / denom);
+    m[e] = mn; v[e] = vn; param[e] = p;
+    image[fwd[e]] = p;
+    if (row[e] >= 0) rows[row[e]] = p;
+    if (e < act_dim) std[e] = mrp::exp_f32(p);
+}
+
+// the master copy and the row-major image from the policy's image (after mrp_policy_set_params)
+__global__ __launch_bounds__(P_NT) void k_ppo_import(int n_params, const float* __restrict__ image, const int* __restrict__ fwd,
+                                                     const int* __restrict__ row, float* __restrict__ param,
+                                                     float* __restrict__ rows) {
+    const int e = blockIdx.x * P_NT + threadIdx.x;
+    if (e >= n_params) return;
+    const float p = image[fwd[e]];
+    param[e] = p;
+    if (row[e] >= 0) rows[row[e]] = p;
+}
+
+__global__ void k_exp(const float* __restrict__ x, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = mrp::exp_f32(x[i]);
+}
+
+thread_local std::string g_ppo_create_error;
+
+inline int pad32(int n) { return (n + 31) & ~31; }
+
+}  // namespace
+
+struct mrp_ppo {
+    mrp_policy* policy = nullptr;
+    int device = 0, max_batch = 0, max_chunks = 0, n_params = 0, n_tiles = 0, n_elems = 0, seen_version = -1;
+    PpoNet pn = {};
+    float* d_ws = nullptr;        // activations, deltas, terms
+    float* d_rows = nullptr;      // row-major image of the hidden weights
+    float* d_vec = nullptr;       // param, grad, m, v (n_params each), coef
+    float* d_partial = nullptr;   // [max_chunks][n_params]
+    double* d_spart = nullptr;    // [max_chunks][NSTAT]
+    int* d_idx = nullptr;         // fwd[n_params], row[n_params]
+    WTile* d_tiles = nullptr;
+    BElem* d_elems = nullptr;
+    std::string err;
+    float* param() const { return d_vec; }
+    float* grad() const { return d_vec + n_params; }
+    float* m() const { return d_vec + 2 * (size_t)n_params; }
+    float* v() const { return d_vec + 3 * (size_t)n_params; }
+    float* coef() const { return d_vec + 4 * (size_t)n_params; }
+};
+
+namespace {
+
+// gradients and statistics of one minibatch into `d_grad` (the object's own vector when null) and d_stats
+int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const float* obs, const float* actions, const float* old_lp,
+                    const float* adv, const float* ret, float clip, float ent_coef, double vf_coef, double max_norm, float* d_grad,
+                    float* d_stats) {
+    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
+    if (B < 1) return bad("B < 1");
+    if (B > o->max_batch) return bad("B > max_batch");
+    if (!obs || !actions || !old_lp || !adv || !ret || !d_stats) return bad("null pointer");
+    // the arrays' extents are known, so an output that overlaps an input anywhere (a view into the same
+    // allocation at an offset) is refused, not only one that starts at the same address
+    const size_t nB = (size_t)B;
+    const float* ins[] = {obs, actions, old_lp, adv, ret};
+    const size_t in_n[] = {nB * o->pn.net.obs_dim, nB * o->pn.net.act_dim, nB, nB, nB};
+    auto overlap = [](const float* a, size_t na, const float* b, size_t nb) {
+        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+        return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
+    };
+    for (int i = 0; i < 5; ++i) {
+        if (overlap(d_stats, NSTAT, ins[i], in_n[i]) || (d_grad && overlap(d_grad, (size_t)o->n_params, ins[i], in_n[i])))
+            return bad("an output aliases an input");
+    }
+    if (d_grad && overlap(d_grad, (size_t)o->n_params, d_stats, NSTAT)) return bad("the two outputs overlap");
+    mrp_policy* p = o->policy;
+    if (!p->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    PCHK(o, hipSetDevice(o->device));
+    const int P = o->n_params, pb = (P + P_NT - 1) / P_NT;
+    if (o->seen_version != p->version) {
+        hipLaunchKernelGGL(k_ppo_import, dim3(pb), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P, o->param(), o->d_rows);
+        o->seen_version = p->version;
+    }
+    const int n_chunks = (B + CHUNK - 1) / CHUNK;
+    hipLaunchKernelGGL(k_ppo_fb, dim3((B + P_TILE - 1) / P_TILE), dim3(P_NT), 0, st, o->pn, B, obs, actions, old_lp, adv, ret, clip,
+                       (float)(2.0 * vf_coef), (float)(1.0 / (double)B));
+    const int waves = o->n_tiles * n_chunks;
+    hipLaunchKernelGGL(k_ppo_wgrad, dim3((waves + 3) / 4), dim3(P_NT), 0, st, o->d_tiles, o->n_tiles, B, obs, o->pn.net.obs_dim,
+                       o->d_partial, P);
+    hipLaunchKernelGGL(k_ppo_bsum, dim3(n_chunks, (o->n_elems + P_NT - 1) / P_NT + 1), dim3(P_NT), 0, st, o->d_elems, o->n_elems, B,
+                       o->pn.sterm, o->d_partial, P, o->d_spart);
+    float* g = d_grad ? d_grad : o->grad();
+    hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g);
+    hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats);
+    PCHK(o, hipGetLastError());
+    return MRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* mrp_ppo_last_error(const mrp_ppo* o) { return o ? o->err.c_str() : g_ppo_create_error.c_str(); }
+
+int mrp_ppo_n_params(const mrp_ppo* o) { return o ? o->n_params : MRP_E_ARG; }
+
+void mrp_ppo_destroy(mrp_ppo* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    void* ptrs[] = {o->d_ws, o->d_rows, o->d_vec, o->d_partial, o->d_spart, o->d_idx, o->d_tiles, o->d_elems};
+    for (void* q : ptrs)
+        if (q) (void)hipFree(q);
+    delete o;
+}
+
+int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out) {
+    std::string& err = g_ppo_create_error;
+    err.clear();
+    auto bad = [&](const char* what) { err = std::string("mrp_ppo_create: ") + what; return MRP_E_ARG; };
+    if (!out) return bad("null out");
+    *out = nullptr;
+    if (!policy) return bad("null policy");
+    if (max_batch < 1 || max_batch > (1 << 20)) return bad("max_batch outside 1..1048576");
+    mrp_ppo* o = new (std::nothrow) mrp_ppo();
+    if (!o) return bad("out of host memory");
+    o->policy = policy; o->device = policy->device; o->max_batch = max_batch;
+    o->max_chunks = (max_batch + CHUNK - 1) / CHUNK;
+    const Net& net = policy->net;
+    PpoNet& pn = o->pn;
+    pn.net = net;
+    const int S = net.n_shared, NP = net.n_pi, NV = net.n_vf, nl = S + NP + NV, A = net.act_dim, D = net.obs_dim;
+    const float* image = policy->d_params;
+    std::vector<const Layer*> layers;
+    for (int i = 0; i < S; ++i) layers.push_back(&net.shared[i]);
+    for (int i = 0; i < NP; ++i) layers.push_back(&net.pi[i]);
+    for (int i = 0; i < NV; ++i) layers.push_back(&net.vf[i]);
+    // the input of hidden layer li: -1 the observations, else a layer index
+    auto input_of = [&](int li) { return li == 0 ? -1 : (li == S || li == S + NP) ? S - 1 : li - 1; };
+    // flat order: log_std, then per layer weight [out][in] and bias; the two image indices of every element
+    std::vector<int> fwd, row;
+    std::vector<int> w_off(nl + 2), b_off(nl + 2);
+    for (int i = 0; i < A; ++i) { fwd.push_back((int)(net.log_std - image) + i); row.push_back(-1); }
+    size_t rows_floats = 0;
+    std::vector<size_t> rows_at(nl);
+    for (int li = 0; li < nl; ++li) {
+        const Layer& L = *layers[li];
+        rows_at[li] = rows_floats;
+        const int Kpad = pad32(L.K);
+        w_off[li] = (int)fwd.size();
+        for (int j = 0; j < L.N; ++j)
+            for (int k = 0; k < L.K; ++k) {
+                fwd.push_back((int)(L.w - image) + k * L.Npad + j);
+                row.push_back((int)(rows_floats + (size_t)j * Kpad + k));
+            }
+        b_off[li] = (int)fwd.size();
+        for (int j = 0; j < L.N; ++j) { fwd.push_back((int)(L.b - image) + j); row.push_back(-1); }
+        rows_floats += (size_t)L.N * Kpad;
+    }
+    w_off[nl] = (int)fwd.size();
+    for (int i = 0; i < A; ++i)
+        for (int k = 0; k < net.act.K; ++k) { fwd.push_back((int)(net.act.w - image) + i * net.act.Kpad + k); row.push_back(-1); }
+    b_off[nl] = (int)fwd.size();
+    for (int i = 0; i < A; ++i) { fwd.push_back((int)(net.act.b - image) + i); row.push_back(-1); }
+    w_off[nl + 1] = (int)fwd.size();
+    for (int k = 0; k < net.val.K; ++k) { fwd.push_back((int)(net.val.w - image) + k); row.push_back(-1); }
+    b_off[nl + 1] = (int)fwd.size();
+    fwd.push_back((int)(net.val.b - image)); row.push_back(-1);
+    const int P = o->n_params = (int)fwd.size();
+    // the workspace: activations and deltas per hidden layer, the heads' deltas, the log_std and statistics terms
+    size_t ws = 0;
+    std::vector<size_t> act_at(nl), delta_at(nl);
+    for (int li = 0; li < nl; ++li) {
+        act_at[li] = ws; ws += (size_t)max_batch * layers[li]->Npad;
+        delta_at[li] = ws; ws += (size_t)max_batch * layers[li]->Npad;
+    }
+    const size_t dact_at = ws, dval_at = ws + (size_t)max_batch * HW, ls_at = ws + 2 * (size_t)max_batch * HW;
+    const size_t st_at = ws + 3 * (size_t)max_batch * HW;
+    ws = st_at + (size_t)max_batch * SW;
+    hipError_t e = hipSetDevice(o->device);
+    auto alloc = [&](void** q, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(q, bytes ? bytes : 4);
+        if (e == hipSuccess) e = hipMemset(*q, 0, bytes ? bytes : 4);
+    };
+    alloc((void**)&o->d_ws, ws * sizeof(float));
+    // one padded row more than the images hold: with a single output row (K2 == 0) hidden_layer's tail still
+    // requests k-step 0 for both halves of the wave, and the lanes of the upper half read the row behind
+    // the image (the value is not used; in k_policy's image the bias follows the weights)
+    alloc((void**)&o->d_rows, (rows_floats + P_MAXW) * sizeof(float));
+    alloc((void**)&o->d_vec, (4 * (size_t)P + 4) * sizeof(float));
+    alloc((void**)&o->d_partial, (size_t)o->max_chunks * P * sizeof(float));
+    alloc((void**)&o->d_spart, (size_t)o->max_chunks * NSTAT * sizeof(double));
+    alloc((void**)&o->d_idx, 2 * (size_t)P * sizeof(int));
+    if (e == hipSuccess) {
+        for (int li = 0; li < nl; ++li) {
+            const Layer& L = *layers[li];
+            pn.act[li] = o->d_ws + act_at[li];
+            pn.delta[li] = o->d_ws + delta_at[li];
+            pn.bwd[li] = Layer{o->d_rows + rows_at[li], nullptr, L.N, L.K, pad32(L.K)};
+        }
+        pn.delta[L_ACT] = o->d_ws + dact_at; pn.delta[L_VAL] = o->d_ws + dval_at;
+        pn.lsterm = o->d_ws + ls_at; pn.sterm = o->d_ws + st_at;
+    }
+    // the weight-gradient tiles and the bias elements
+    std::vector<WTile> tiles;
+    std::vector<BElem> elems;
+    auto add_layer = [&](const float* delta, int dstride, int in, int N, int K, int woff, int boff) {
+        const float* x = in < 0 ? nullptr : pn.act[in];
+        const int xstride = in < 0 ? D : layers[in]->Npad;
+        for (int j0 = 0; j0 < N; j0 += 32)
+            for (int k0 = 0; k0 < K; k0 += 32) tiles.push_back(WTile{delta, x, dstride, xstride, j0, k0, N, K, woff});
+        for (int j = 0; j < N; ++j) elems.push_back(BElem{delta + j, dstride, boff + j});
+    };
+    if (e == hipSuccess) {
+        for (int i = 0; i < A; ++i) elems.push_back(BElem{pn.lsterm + i, HW, i});
+        for (int li = 0; li < nl; ++li) add_layer(pn.delta[li], layers[li]->Npad, input_of(li), layers[li]->N, layers[li]->K, w_off[li], b_off[li]);
+        const int in_pi = NP ? S + NP - 1 : S - 1, in_vf = NV ? S + NP + NV - 1 : S - 1;
+        add_layer(pn.delta[L_ACT], HW, in_pi, A, net.act.K, w_off[nl], b_off[nl]);
+        add_layer(pn.delta[L_VAL], HW, in_vf, 1, net.val.K, w_off[nl + 1], b_off[nl + 1]);
+        o->n_tiles = (int)tiles.size(); o->n_elems = (int)elems.size();
+        alloc((void**)&o->d_tiles, tiles.size() * sizeof(WTile));
+        alloc((void**)&o->d_elems, elems.size() * sizeof(BElem));
+    }
+    if (e == hipSuccess) e = hipMemcpy(o->d_idx, fwd.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_idx + P, row.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_tiles, tiles.data(), tiles.size() * sizeof(WTile), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_elems, elems.data(), elems.size() * sizeof(BElem), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        err = std::string("mrp_ppo_create: ") + hipGetErrorString(e);
+        mrp_ppo_destroy(o);
+        return MRP_E_HIP;
+    }
+    *out = o;
+    return MRP_OK;
+}
+
+int mrp_ppo_grad_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs, const float* d_actions, const float* d_old_log_probs,
+                        const float* d_advantages, const float* d_returns, float clip_range, float ent_coef, double vf_coef,
+                        float* d_grad, float* d_stats) {
+    if (!o) return MRP_E_ARG;
+    if (!d_grad) { o->err = "mrp_ppo_grad_device: null pointer"; return MRP_E_ARG; }
+    return ppo_grad_launch(o, "mrp_ppo_grad_device", (hipStream_t)hip_stream, B, d_obs, d_actions, d_old_log_probs, d_advantages,
+                           d_returns, clip_range, ent_coef, vf_coef, 1.0, d_grad, d_stats);
+}
+
+int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs, const float* d_actions, const float* d_old_log_probs,
+                        const float* d_advantages, const float* d_returns, float clip_range, float ent_coef, double vf_coef,
+                        double max_grad_norm, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
+                        float step_size, float eps, float* d_stats) {
+    if (!o) return MRP_E_ARG;
+    const int rc = ppo_grad_launch(o, "mrp_ppo_step_device", (hipStream_t)hip_stream, B, d_obs, d_actions, d_old_log_probs,
+                                   d_advantages, d_returns, clip_range, ent_coef, vf_coef, max_grad_norm, nullptr, d_stats);
+    if (rc != MRP_OK) return rc;
+    const int P = o->n_params;
+    mrp_policy* p = o->policy;
+    const AdamK k{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps};
+    hipLaunchKernelGGL(k_ppo_adam, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, (hipStream_t)hip_stream, P, p->net.act_dim, o->grad(),
+                       o->coef(), o->param(), o->m(), o->v(), o->d_idx, o->d_idx + P, p->d_params, o->d_rows,
+                       const_cast<float*>(p->net.std), k);
+    PCHK(o, hipGetLastError());
+    return MRP_OK;
+}
+
+int mrp_ppo_get_state(mrp_ppo* o, float* m, float* v) {
+    if (!o) return MRP_E_ARG;
+    if (!m || !v) { o->err = "mrp_ppo_get_state: null pointer"; return MRP_E_ARG; }
+    PCHK(o, hipSetDevice(o->device));
+    PCHK(o, hipDeviceSynchronize());
+    PCHK(o, hipMemcpy(m, o->m(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    PCHK(o, hipMemcpy(v, o->v(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return MRP_OK;
+}
+
+int mrp_selftest_exp(int device, const float* x, float* out, int n) {
+    if (!x || !out || n <= 0) return MRP_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
+    float *dx = nullptr, *dy = nullptr;
+    const size_t bytes = (size_t)n * sizeof(float);
+    int rc = MRP_E_HIP;
+    if (hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&dy, bytes) == hipSuccess &&
+        hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_exp, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = MRP_OK;
+    }
+    if (dx) (void)hipFree(dx);
+    if (dy) (void)hipFree(dy);
+    return rc;
+}
+
+}  // extern "C"

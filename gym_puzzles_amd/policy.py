@@ -110,9 +110,11 @@ def _activate(x, activation):
 class PolicyParams:
     """The arrays of one policy, float32 in torch's ``[out, in]`` layout: ``shared`` / ``pi`` / ``vf``
     are lists of ``(weight, bias)``, ``action`` and ``value`` the heads' ``(weight, bias)``.  Raises
-    ``ValueError`` for shapes that do not chain or lie outside the limits."""
+    ``ValueError`` for shapes that do not chain or lie outside the limits.  ``std`` is
+    ``float32(exp(float64(log_std)))`` unless given: parameters exported from the device after a PPO
+    step carry the device's ``std`` bits (``ppo.exp_ref``)."""
 
-    def __init__(self, shared, pi, vf, action, value, log_std, activation="tanh"):
+    def __init__(self, shared, pi, vf, action, value, log_std, activation="tanh", std=None):
         f = lambda wb: (np.ascontiguousarray(wb[0], _f32), np.ascontiguousarray(wb[1], _f32))  # noqa: E731
         self.shared, self.pi, self.vf = [f(x) for x in shared], [f(x) for x in pi], [f(x) for x in vf]
         self.action, self.value = f(action), f(value)
@@ -142,6 +144,10 @@ class PolicyParams:
             raise ValueError(f"policy: log_std is {self.log_std.shape}, expected ({self.act_dim},)")
         check_arch(self.obs_dim, self.act_dim, len(self.shared), len(self.pi), len(self.vf), self.widths)
         self.std = np.exp(self.log_std.astype(_f64)).astype(_f32)
+        if std is not None:
+            self.std = np.ascontiguousarray(std, _f32).reshape(-1).copy()
+            if self.std.shape != (self.act_dim,):
+                raise ValueError(f"policy: std is {self.std.shape}, expected ({self.act_dim},)")
 
     @property
     def widths(self):
@@ -298,6 +304,32 @@ class DevicePolicy:
         bs = (ctypes.c_void_p * n)(*[b.ctypes.data for _, b in layers])
         self._check_rc(self._L.mrp_policy_set_params(self._h, ws, bs, params.log_std.ctypes.data, params.std.ctypes.data))
         self.params = params
+
+    def get_params(self):
+        """The device's parameters as a ``PolicyParams`` (``std`` included), e.g. after ``DevicePPO``
+        steps: the inverse of ``set_params`` (synchronises the device)."""
+        if self.params is None:
+            raise ValueError("DevicePolicy.get_params: no parameters yet (set_params)")
+        S, Pn, V = self.arch
+        kt = self.widths[S - 1] if S else self.obs_dim
+        # a layer's inputs: the observation, the trunk's output at the head of a tower, else the layer before
+        ins = [self.obs_dim if i == 0 and S else kt if i in (S, S + Pn) else self.widths[i - 1] for i in range(len(self.widths))]
+        kp = self.widths[S + Pn - 1] if Pn else kt
+        kv = self.widths[S + Pn + V - 1] if V else kt
+        layers = [(np.zeros((n, k), _f32), np.zeros(n, _f32)) for n, k in zip(self.widths, ins)]
+        layers += [(np.zeros((self.act_dim, kp), _f32), np.zeros(self.act_dim, _f32)), (np.zeros((1, kv), _f32), np.zeros(1, _f32))]
+        log_std, std = np.zeros(self.act_dim, _f32), np.zeros(self.act_dim, _f32)
+        ws = (ctypes.c_void_p * len(layers))(*[w.ctypes.data for w, _ in layers])
+        bs = (ctypes.c_void_p * len(layers))(*[b.ctypes.data for _, b in layers])
+        self._check_rc(self._L.mrp_policy_get_params(self._h, ws, bs, log_std.ctypes.data, std.ctypes.data))
+        nl = len(self.widths)
+        return PolicyParams(layers[:S], layers[S:S + Pn], layers[S + Pn:nl], layers[nl], layers[nl + 1], log_std,
+                            self.activation, std=std)
+
+    def state_dict(self):
+        """The device's parameters as arrays under SB3's names: the inverse of ``params_from_state_dict``."""
+        from .ppo import state_dict_from_params
+        return state_dict_from_params(self.get_params())
 
     def _obs(self, obs):
         import torch

@@ -337,6 +337,51 @@ int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const fl
 int mrp_policy_values_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, float* d_values);
 /* Device self-test of the policy's tanh rule (mrp_math.h tanh_f32) on n host inputs (host output). */
 int mrp_selftest_tanh(int device, const float* x, float* out, int n);
+/* The device's parameters in mrp_policy_set_params's layout, plus std: its inverse, e.g. after
+ * mrp_ppo_step_device.  Synchronises the device.  MRP_E_ARG: a null pointer; MRP_E_STATE before
+ * mrp_policy_set_params. */
+int mrp_policy_get_params(mrp_policy* p, float* const* weights, float* const* biases, float* log_std, float* std);
+
+/* ---------------------------------------------------------------------------------------------
+ * Device PPO update: one optimiser step of SB3's PPO.train() on a minibatch (evaluate_actions, the
+ * clipped surrogate / value / entropy losses, the backward pass, global grad-norm clipping, Adam),
+ * written into the policy's device parameters in place, with no host synchronisation and no
+ * atomics.  The rule, which the kernels match bit for bit, is gym_puzzles_amd.ppo.ppo_grad_ref /
+ * adam_ref (DESIGN.md "Device PPO update").  The flat parameter order is SB3's parameters():
+ * log_std, then trunk, policy tower, value tower, action head, value head, each weight row-major
+ * [out][in], then bias.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct mrp_ppo mrp_ppo;
+/* The optimiser of one policy (which must outlive it; one mrp_ppo per policy): master parameters,
+ * gradient, Adam moments (zero) and a workspace for minibatches of up to max_batch samples.
+ * MRP_E_ARG: a null pointer, max_batch outside 1..1048576 (message: mrp_ppo_last_error(NULL)).  A
+ * later mrp_policy_set_params is picked up by the next call; the moments stay. */
+int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out);
+void mrp_ppo_destroy(mrp_ppo* o);
+const char* mrp_ppo_last_error(const mrp_ppo* o);
+/* The length of the flat parameter vector. */
+int mrp_ppo_n_params(const mrp_ppo* o);
+/* Gradients and statistics only: d_grad [n_params] takes the flat gradient before clipping, d_stats
+ * [5] the policy loss, value loss, entropy loss, approx_kl and clip fraction.  Inputs: float32 device
+ * arrays d_obs [B][obs_dim], d_actions [B][act_dim] (the stored, unclipped actions), d_old_log_probs,
+ * d_advantages, d_returns [B].  Parameters and moments are not written.  MRP_E_ARG: B < 1, B >
+ * max_batch, a null pointer, an output that overlaps an input or the other output; MRP_E_STATE before
+ * mrp_policy_set_params.  Asynchronous. */
+int mrp_ppo_grad_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs, const float* d_actions,
+                        const float* d_old_log_probs, const float* d_advantages, const float* d_returns, float clip_range,
+                        float ent_coef, double vf_coef, float* d_grad, float* d_stats);
+/* Gradients, clip and Adam; the policy's parameters (std = exp_f32(log_std) included) are updated
+ * in place for the next mrp_policy_act_device on the same stream.  The Adam scalars of step t are
+ * computed by the caller in float64 and passed as float32: beta1, 1 - beta1, beta2, 1 - beta2,
+ * sqrt(1 - beta2^t), lr / (1 - beta1^t), eps.  Errors as mrp_ppo_grad_device.  Asynchronous. */
+int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs, const float* d_actions,
+                        const float* d_old_log_probs, const float* d_advantages, const float* d_returns, float clip_range,
+                        float ent_coef, double vf_coef, double max_grad_norm, float beta1, float one_minus_beta1, float beta2,
+                        float one_minus_beta2, float sqrt_bc2, float step_size, float eps, float* d_stats);
+/* Host copies of Adam's moments, n_params floats each.  Synchronises the device. */
+int mrp_ppo_get_state(mrp_ppo* o, float* m, float* v);
+/* Device self-test of the exp rule (mrp_math.h exp_f32) on n host inputs (host output). */
+int mrp_selftest_exp(int device, const float* x, float* out, int n);
 
 #ifdef __cplusplus
 }
