@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from ._device import Handle
 from .spawn import ENV_IDS, ENV_VERSION  # noqa: F401  (ENV_IDS: the package's public name table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -92,11 +93,12 @@ ABI = {
     "mrp_policy_create": (_i, [_i] * 6 + [_ip, _i, _PP]),
     "mrp_policy_destroy": (None, [_P]),
     "mrp_policy_last_error": (ctypes.c_char_p, [_P]),
-    "mrp_policy_set_params": (_i, [_P, _PP, _PP, _P, _P]),
+    "mrp_policy_n_params": (_i, [_P]),
+    "mrp_policy_set_params": (_i, [_P, _P, _P]),
     "mrp_policy_act_device": (_i, [_P, _P, _i, _P, _P, _u64, _u64, _u64, _i] + [_P] * 5),
     "mrp_policy_values_device": (_i, [_P, _P, _i, _P, _P]),
     "mrp_selftest_tanh": (_i, [_i, _P, _P, _i]),
-    "mrp_policy_get_params": (_i, [_P, _PP, _PP, _P, _P]),
+    "mrp_policy_get_params": (_i, [_P, _P, _P]),
     "mrp_ppo_create": (_i, [_P, _i, _PP]),
     "mrp_ppo_destroy": (None, [_P]),
     "mrp_ppo_last_error": (ctypes.c_char_p, [_P]),
@@ -162,18 +164,15 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-class Batch:
+class Batch(Handle):
     """N independent MultiRobotPuzzle worlds on one GPU (one ``mrp_ctx``)."""
 
+    _DESTROY, _LAST_ERROR = "mrp_destroy", "mrp_last_error"
+
     def __init__(self, env_id: int, n_lanes: int, device: int = 0, seed: int = 0, lane_offset: int = 0):
-        L = load()
         self.env_id, self.n_lanes, self.device = env_id, n_lanes, device
         self.__dict__.update(env_dims(env_id))
-        h = ctypes.c_void_p()
-        rc = L.mrp_create(env_id, n_lanes, device, seed, lane_offset, ctypes.byref(h))
-        if rc != MRP_OK:
-            raise MrpError(f"mrp_create failed ({rc}): {L.mrp_last_error(None).decode()}")
-        self._h = h
+        self._open("mrp_create", env_id, n_lanes, device, seed, lane_offset)
         self.obs = np.zeros((n_lanes, self.obs_dim), np.float32)
         self.reward = np.zeros(n_lanes, np.float32)
         self.reward64 = np.zeros(n_lanes, np.float64)   # the reference's Python-float rewards
@@ -183,25 +182,9 @@ class Batch:
         self.terminal_obs = np.zeros((n_lanes, self.obs_dim), np.float32)
         # the output arrays live as long as the batch: their addresses are taken once, so a host step
         # costs one ctypes call (the gym-style single env steps one lane per call)
-        self._L = L
         self._out = (self.obs.ctypes.data, self.reward.ctypes.data, self.reward64.ctypes.data, self.done.ctypes.data,
                      self.truncated.ctypes.data, self.status.ctypes.data)
         self._term = self.terminal_obs.ctypes.data
-
-    def _check(self, rc):
-        if rc != MRP_OK:
-            raise MrpError(load().mrp_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            load().mrp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def handle(self):
@@ -216,27 +199,27 @@ class Batch:
         agentDistance = (0.1 if v0 else 0.25) if agentDistance is None else agentDistance
         blockDelta = (50 if v0 else 25) if blockDelta is None else blockDelta
         blockDistance = (0.025 if v0 else 0.1) if blockDistance is None else blockDistance
-        self._check(load().mrp_set_reward_params(self._h, agentDelta, agentDistance, blockDelta, blockDistance,
+        self._check_rc(load().mrp_set_reward_params(self._h, agentDelta, agentDistance, blockDelta, blockDistance,
                                                  puzzleComp, outOfBounds, blkOutOfBounds))
 
     def update_params(self, timestep, decay):
-        self._check(load().mrp_update_params(self._h, float(timestep), float(decay)))
+        self._check_rc(load().mrp_update_params(self._h, float(timestep), float(decay)))
 
     def update_goal(self, epoch, nb_epochs):
-        self._check(load().mrp_update_goal(self._h, float(epoch), float(nb_epochs)))
+        self._check_rc(load().mrp_update_goal(self._h, float(epoch), float(nb_epochs)))
 
     def set_frameskip(self, frameskip: int):
         """world.Step calls per env step (MultiRobotPuzzle2(frameskip=k), multi_robot_puzzle_02.py:476-478)."""
-        self._check(load().mrp_set_frameskip(self._h, int(frameskip)))
+        self._check_rc(load().mrp_set_frameskip(self._h, int(frameskip)))
 
     def set_auto_reset(self, enabled: bool):
-        self._check(load().mrp_set_auto_reset(self._h, 1 if enabled else 0))
+        self._check_rc(load().mrp_set_auto_reset(self._h, 1 if enabled else 0))
 
     def reset(self, draws=None, actions=None, mask=None) -> np.ndarray:
         d = None if draws is None else np.ascontiguousarray(draws, np.float64).reshape(self.n_lanes, self.n_draws)
         a = None if actions is None else np.ascontiguousarray(actions, np.float32).reshape(self.n_lanes, self.act_dim)
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(self.n_lanes)
-        self._check(load().mrp_reset(self._h, _p(m), _p(d), _p(a), _p(self.obs)))
+        self._check_rc(load().mrp_reset(self._h, _p(m), _p(d), _p(a), _p(self.obs)))
         return self.obs
 
     def step(self, actions=None, want_terminal_obs=False):
@@ -247,29 +230,27 @@ class Batch:
             if a.size != self.n_lanes * self.act_dim:
                 raise ValueError(f"actions: expected {self.n_lanes} x {self.act_dim} values, got shape {a.shape}")
             ap = a.ctypes.data
-        rc = self._L.mrp_step_ex(self._h, ap, *self._out, self._term if want_terminal_obs else None)
-        if rc != MRP_OK:
-            self._check(rc)
+        self._check_rc(self._L.mrp_step_ex(self._h, ap, *self._out, self._term if want_terminal_obs else None))
         return self.obs, self.reward, self.done, self.truncated
 
     def step_device(self, d_actions, d_obs, d_reward=None, d_done=None, d_trunc=None, d_status=None, d_term=None,
                     d_reward64=None):
         """Asynchronous step on device pointers (ints, e.g. torch ``tensor.data_ptr()``);
         ``d_reward64`` optionally receives the float64 rewards."""
-        self._check(load().mrp_step_device_ex(self._h, d_actions, d_obs, d_reward, d_reward64, d_done, d_trunc, d_status,
+        self._check_rc(load().mrp_step_device_ex(self._h, d_actions, d_obs, d_reward, d_reward64, d_done, d_trunc, d_status,
                                               d_term))
 
     def step_n_device(self, n_steps, d_actions, d_obs, d_reward=None, d_done=None, d_trunc=None, d_status=None,
                       d_term=None, d_reward64=None):
         """``n_steps`` consecutive steps in one launch (mrp_step_n_device); every array holds
         ``n_steps`` rows of ``n_lanes`` (step-major), device pointers as in step_device."""
-        self._check(load().mrp_step_n_device(self._h, int(n_steps), d_actions, d_obs, d_reward, d_reward64, d_done,
+        self._check_rc(load().mrp_step_n_device(self._h, int(n_steps), d_actions, d_obs, d_reward, d_reward64, d_done,
                                              d_trunc, d_status, d_term))
 
     def set_schedule(self, mode):
         """Lane scheduling (mrp_set_schedule): 0 off, 1 costliest-first dispatch, 2 issue priority
         from the previous step's cost, 3 both (True = 1); results are identical in every mode."""
-        self._check(load().mrp_set_schedule(self._h, int(mode)))
+        self._check_rc(load().mrp_set_schedule(self._h, int(mode)))
 
     def get_schedule(self) -> int:
         """The lane scheduling mode in force (mrp_get_schedule): mrp_create's per-env default until
@@ -279,55 +260,55 @@ class Batch:
     def set_seed(self, seed: int):
         """Re-key the device RNG (later resets and synthetic actions); lanes, parameters, stream
         and time limit are kept."""
-        self._check(load().mrp_set_seed(self._h, int(seed)))
+        self._check_rc(load().mrp_set_seed(self._h, int(seed)))
 
     def set_time_limit(self, max_episode_steps: int):
-        self._check(load().mrp_set_time_limit(self._h, int(max_episode_steps)))
+        self._check_rc(load().mrp_set_time_limit(self._h, int(max_episode_steps)))
 
     def set_stream(self, stream_ptr):
-        self._check(load().mrp_set_stream(self._h, stream_ptr))
+        self._check_rc(load().mrp_set_stream(self._h, stream_ptr))
 
     def synchronize(self):
-        self._check(load().mrp_synchronize(self._h))
+        self._check_rc(load().mrp_synchronize(self._h))
 
     def bodies(self) -> np.ndarray:
         out = np.zeros((self.n_lanes, 6 * (self.n_agents + self.n_blocks)), np.float32)
-        self._check(load().mrp_get_bodies(self._h, _p(out)))
+        self._check_rc(load().mrp_get_bodies(self._h, _p(out)))
         return out
 
     def flags(self) -> np.ndarray:
         out = np.zeros((self.n_lanes, self.n_agents + 1), np.int32)
-        self._check(load().mrp_get_flags(self._h, _p(out)))
+        self._check_rc(load().mrp_get_flags(self._h, _p(out)))
         return out
 
     def faults(self) -> np.ndarray:
         """Per-lane loop-guard fault codes (0 = none; include/mrp.h mrp_get_faults)."""
         out = np.zeros(self.n_lanes, np.int32)
-        self._check(load().mrp_get_faults(self._h, _p(out)))
+        self._check_rc(load().mrp_get_faults(self._h, _p(out)))
         return out
 
     def counters(self):
         a = np.zeros(1, np.int64)
         b = np.zeros(1, np.int64)
-        self._check(load().mrp_counters(self._h, _p(a), _p(b)))
+        self._check_rc(load().mrp_counters(self._h, _p(a), _p(b)))
         return int(a[0]), int(b[0])
 
     def counters_ex(self) -> dict:
         """Per-batch counters since creation (mrp_counters_ex; SURVEY.md 5 metrics)."""
         out = np.zeros(8, np.int64)
-        self._check(load().mrp_counters_ex(self._h, _p(out)))
+        self._check_rc(load().mrp_counters_ex(self._h, _p(out)))
         return {k: int(v) for k, v in zip(COUNTER_NAMES, out)}
 
     def get_state(self) -> np.ndarray:
         w = load().mrp_state_words(self.env_id)
         out = np.zeros((self.n_lanes, w), np.uint32)
-        self._check(load().mrp_get_state(self._h, _p(out)))
+        self._check_rc(load().mrp_get_state(self._h, _p(out)))
         return out
 
     def get_goals(self) -> np.ndarray:
         """block_final_pos per lane: float64 [n_lanes, n_blocks, 3] (v0 px, v2 scaled units)."""
         out = np.zeros((self.n_lanes, self.n_blocks, 3), np.float64)
-        self._check(load().mrp_get_goals(self._h, _p(out)))
+        self._check_rc(load().mrp_get_goals(self._h, _p(out)))
         return out
 
     def render(self, lanes=None, width: int | None = None, height: int | None = None) -> np.ndarray:
@@ -337,19 +318,19 @@ class Batch:
         width, height = width or w0, height or h0
         sel = np.ascontiguousarray(np.arange(self.n_lanes) if lanes is None else np.atleast_1d(lanes), np.int32)
         out = np.zeros((len(sel), height, width, 3), np.uint8)
-        self._check(load().mrp_render(self._h, _p(sel), len(sel), width, height, _p(out)))
+        self._check_rc(load().mrp_render(self._h, _p(sel), len(sel), width, height, _p(out)))
         return out
 
     def render_device(self, d_lanes_ptr: int, n: int, width: int, height: int, d_rgb_ptr: int):
         """Asynchronous render into a device buffer (e.g. a torch uint8 tensor's data_ptr())."""
-        self._check(load().mrp_render_device(self._h, ctypes.c_void_p(d_lanes_ptr), n, width, height, ctypes.c_void_p(d_rgb_ptr)))
+        self._check_rc(load().mrp_render_device(self._h, ctypes.c_void_p(d_lanes_ptr), n, width, height, ctypes.c_void_p(d_rgb_ptr)))
 
     def pixels_device(self, width: int, height: int, channels: int, depth: int, d_done_ptr, d_prev_ptr, d_next_ptr: int):
         """Asynchronous frame-stack update of every lane on device pointers (mrp_pixels_device):
         uint8 [n_lanes, depth, height, width, channels] ``next`` from ``prev`` (0 / None: fresh stacks)
         and the lanes' current state; lanes whose ``done`` byte (0 / None: none) is set start afresh."""
         ptr = (lambda a: ctypes.c_void_p(a) if a else None)
-        self._check(load().mrp_pixels_device(self._h, int(width), int(height), int(channels), int(depth), ptr(d_done_ptr),
+        self._check_rc(load().mrp_pixels_device(self._h, int(width), int(height), int(channels), int(depth), ptr(d_done_ptr),
                                              ptr(d_prev_ptr), ptr(d_next_ptr)))
 
     def pixels(self, width: int, height: int, channels: int = 3, depth: int = 1, done=None, prev=None) -> np.ndarray:
@@ -366,12 +347,12 @@ class Batch:
             prev = np.ascontiguousarray(prev)
         # sizes the library refuses (MrpError below) never reach the kernel: any buffer will do for them
         out = np.zeros(shape if min(shape) > 0 and depth <= 16 else (1,), np.uint8)
-        self._check(load().mrp_pixels(self._h, int(width), int(height), int(channels), int(depth), _p(d), _p(prev), _p(out)))
+        self._check_rc(load().mrp_pixels(self._h, int(width), int(height), int(channels), int(depth), _p(d), _p(prev), _p(out)))
         return out
 
     def set_state(self, state: np.ndarray):
         s = np.ascontiguousarray(state, np.uint32)
-        self._check(load().mrp_set_state(self._h, _p(s)))
+        self._check_rc(load().mrp_set_state(self._h, _p(s)))
 
 
 def selftest_sincos(x: np.ndarray, device: int = 0):

@@ -32,7 +32,7 @@ POLICY_SOURCES = [("mrp_policy.hip", "mrp_policy.hip.o", None)]
 PPO_SOURCES = [("mrp_ppo.hip", "mrp_ppo.hip.o", None)]
 UNITS = SOURCES + POLICY_SOURCES + PPO_SOURCES
 HEADERS = ("mrp_math.h", "mrp_config.h", "mrp_world.h", "mrp_env.h", "mrp_tables.h", "mrp_ops.h", "mrp_lane.h", "mrp_render.h",
-           "mrp_pixels.h", "mrp_microbench.h", "mrp_policy_net.h")
+           "mrp_pixels.h", "mrp_microbench.h", "mrp_policy_net.h", "mrp_host.h", "mrp_policy_layout.h")
 
 
 def deps(csrc: str = CSRC) -> list[str]:

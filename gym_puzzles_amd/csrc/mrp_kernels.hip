@@ -16,11 +16,13 @@
 #include <vector>
 
 #include "../../include/mrp.h"
+#include "mrp_host.h"
 #include "mrp_math.h"
 #include "mrp_ops.h"
 #include "mrp_tables.h"
 
 using namespace mrp;
+using namespace mrp_host;
 
 namespace {
 __global__ __launch_bounds__(256) void k_sincos(const float* x, float* s, float* c, int n) {
@@ -72,27 +74,6 @@ __global__ __launch_bounds__(256) void k_iota(int* __restrict__ order, int nl) {
 
 // ------------------------------------------------------------------------------ host side
 thread_local std::string g_create_error;
-
-// A temporary buffer of one call, freed when the call returns: device memory, or with PINNED
-// device-mapped host memory.
-template <class T, bool PINNED = false>
-class Scoped {
-    T* p_ = nullptr;
-
-public:
-    Scoped() = default;
-    Scoped(const Scoped&) = delete;
-    Scoped& operator=(const Scoped&) = delete;
-    ~Scoped() {
-        if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
-    }
-    hipError_t alloc(size_t bytes) {
-        if (p_) return hipErrorInvalidValue;   // one buffer per owner: a second one would leak the first
-        return PINNED ? hipHostMalloc((void**)&p_, bytes, hipHostMallocMapped) : hipMalloc((void**)&p_, bytes);
-    }
-    T* get() const { return p_; }
-    T* release() { T* p = p_; p_ = nullptr; return p; }   // mrp_debug_progress hands its buffer to the caller
-};
 }  // namespace
 
 struct mrp_ctx {
@@ -147,15 +128,6 @@ struct mrp_ctx {
                  {(void**)&d_costmax, sizeof(uint32_t)}}};
     }
 };
-
-#define HIPCHK(ctx, expr)                                                   \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) {                                             \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e); \
-            return MRP_E_HIP;                                               \
-        }                                                                   \
-    } while (0)
 
 static int words_for(int env_id) {
     const EnvOps* o = env_ops(env_id);
@@ -309,8 +281,8 @@ int mrp_set_stream(mrp_ctx* ctx, void* hip_stream) {
 
 int mrp_synchronize(mrp_ctx* ctx) {
     if (!ctx) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
@@ -367,17 +339,17 @@ int mrp_set_time_limit(mrp_ctx* ctx, int max_episode_steps) {
 
 int mrp_reset_device(mrp_ctx* ctx, const uint8_t* d_mask, const double* d_draws, const float* d_actions, float* d_obs) {
     if (!ctx || !d_obs) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     env_ops(ctx->env_id)->reset(ctx->stream, ctx->d_state, ctx->n_lanes, d_mask, d_draws, d_actions, d_obs, ctx->params,
                                 ctx->seed, ctx->lane_offset);
-    HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipGetLastError());
     ctx->have_reset = 1;
     return MRP_OK;
 }
 
 int mrp_reset(mrp_ctx* ctx, const uint8_t* mask, const double* draws, const float* actions, float* obs) {
     if (!ctx || !obs) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nl = (size_t)ctx->n_lanes;
     // inputs into the pinned I/O buffer; the kernel reads them and writes the reset rows there
     if (mask) std::memcpy(ctx->h_mask, mask, nl);
@@ -388,7 +360,7 @@ int mrp_reset(mrp_ctx* ctx, const uint8_t* mask, const double* draws, const floa
     int rc = mrp_reset_device(ctx, mask ? ctx->dev(ctx->h_mask) : nullptr, draws ? ctx->dev(ctx->h_draws) : nullptr,
                               actions ? ctx->dev(ctx->h_actions) : nullptr, ctx->dev(ctx->h_obs));
     if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(obs, ctx->h_obs, nl * ctx->obs_dim * sizeof(float));
     return MRP_OK;
 }
@@ -400,18 +372,18 @@ static int step_launch(mrp_ctx* ctx, int n_steps, const float* d_actions, float*
                        uint8_t* d_done, uint8_t* d_trunc, uint8_t* d_status, float* d_term) {
     if (!ctx || !d_obs || n_steps < 1) return MRP_E_ARG;
     if (!ctx->have_reset) { ctx->err = "step() called before reset()"; return MRP_E_STATE; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     const int sched = ctx->schedule;
     StepArgs a{ctx->d_state, ctx->n_lanes, d_actions, d_obs, d_reward, d_reward64, d_done, d_trunc, d_status, d_term,
                ctx->params, ctx->seed, ctx->lane_offset, ctx->auto_reset, ctx->time_limit,
                (sched & 1) ? ctx->d_order : nullptr, sched ? ctx->d_cost : nullptr, (sched & 2) ? ctx->d_costmax : nullptr,
                n_steps};
     env_ops(ctx->env_id)->step(ctx->stream, a);
-    HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipGetLastError());
     if (sched) {   // next step's dispatch order / cost scale (stream-ordered behind this step)
         hipLaunchKernelGGL(k_order, dim3(1), dim3(ORDER_NT), 0, ctx->stream, ctx->d_cost, ctx->n_lanes,
                            (sched & 1) ? ctx->d_order : nullptr, ctx->d_costmax);
-        HIPCHK(ctx, hipGetLastError());
+        MRP_HIPCHK(ctx, hipGetLastError());
     }
     return MRP_OK;
 }
@@ -435,7 +407,7 @@ int mrp_step_device(mrp_ctx* ctx, const float* d_actions, float* d_obs, float* d
 int mrp_step_ex(mrp_ctx* ctx, const float* actions, float* obs, float* reward, double* reward64, uint8_t* done, uint8_t* trunc,
                 uint8_t* status, float* term) {
     if (!ctx || !obs) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nl = (size_t)ctx->n_lanes;
     // one launch that reads the actions from and writes every output into the pinned I/O buffer,
     // one synchronisation, then host copies out of it
@@ -445,7 +417,7 @@ int mrp_step_ex(mrp_ctx* ctx, const float* actions, float* obs, float* reward, d
                                 done ? ctx->dev(ctx->h_done) : nullptr, trunc ? ctx->dev(ctx->h_trunc) : nullptr,
                                 status ? ctx->dev(ctx->h_status) : nullptr, term ? ctx->dev(ctx->h_term) : nullptr);
     if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(obs, ctx->h_obs, nl * ctx->obs_dim * sizeof(float));
     if (reward) std::memcpy(reward, ctx->h_reward, nl * sizeof(float));
     if (reward64) std::memcpy(reward64, ctx->h_reward64, nl * sizeof(double));
@@ -477,56 +449,56 @@ int mrp_set_seed(mrp_ctx* ctx, uint64_t seed) {
 
 int mrp_get_bodies(mrp_ctx* ctx, float* out) {
     if (!ctx || !out) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     env_ops(ctx->env_id)->bodies(ctx->stream, ctx->d_state, ctx->n_lanes, ctx->d_bodies, nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_bodies, (size_t)ctx->n_lanes * 6 * (ctx->n_agents + ctx->n_blocks) * sizeof(float),
+    MRP_HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_bodies, (size_t)ctx->n_lanes * 6 * (ctx->n_agents + ctx->n_blocks) * sizeof(float),
                                hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
 int mrp_get_faults(mrp_ctx* ctx, int32_t* out) {
     if (!ctx || !out) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     int32_t* d = (int32_t*)ctx->d_flags;   // [n_lanes][n_agents+1] >= n_lanes words
     env_ops(ctx->env_id)->faults(ctx->stream, ctx->d_state, ctx->n_lanes, d);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, d, (size_t)ctx->n_lanes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipMemcpyAsync(out, d, (size_t)ctx->n_lanes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
 int mrp_get_flags(mrp_ctx* ctx, int32_t* out) {
     if (!ctx || !out) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     env_ops(ctx->env_id)->bodies(ctx->stream, ctx->d_state, ctx->n_lanes, nullptr, ctx->d_flags);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_flags, (size_t)ctx->n_lanes * (ctx->n_agents + 1) * sizeof(int32_t),
+    MRP_HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_flags, (size_t)ctx->n_lanes * (ctx->n_agents + 1) * sizeof(int32_t),
                                hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
 int mrp_get_state(mrp_ctx* ctx, uint32_t* out) {
     if (!ctx || !out) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nl = (size_t)ctx->n_lanes, nw = (size_t)ctx->words;
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_state, nl * nw * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_state, nl * nw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
 int mrp_set_state(mrp_ctx* ctx, const uint32_t* in) {
     if (!ctx || !in) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nl = (size_t)ctx->n_lanes, nw = (size_t)ctx->words;
     // k_step moves only the contact slots below a lane's high-water mark cHW, so an understated mark
     // is raised to cover the lane's non-initial slots before the upload (StateIO::repair_marks)
     std::vector<uint32_t> st(in, in + nl * nw);
     env_ops(ctx->env_id)->repair_marks(st.data(), nl);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, st.data(), nl * nw * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, st.data(), nl * nw * 4, hipMemcpyHostToDevice, ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_reset = 1;
     return MRP_OK;
 }
@@ -542,11 +514,11 @@ int mrp_counters(mrp_ctx* ctx, int64_t* toi_events, int64_t* pos_iters) {
 
 int mrp_counters_ex(mrp_ctx* ctx, int64_t* out8) {
     if (!ctx || !out8) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     env_ops(ctx->env_id)->counters(ctx->stream, ctx->d_state, ctx->n_lanes, ctx->d_ctr);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out8, ctx->d_ctr, CTR_N * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    MRP_HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipMemcpyAsync(out8, ctx->d_ctr, CTR_N * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    MRP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return MRP_OK;
 }
 
@@ -663,11 +635,11 @@ int mrp_render_device(mrp_ctx* ctx, const int32_t* d_lanes, int n, int width, in
     if (!ctx->have_reset) { ctx->err = "mrp_render: call mrp_reset first"; return MRP_E_STATE; }
     mrpr::RenderArgs A;
     if (render_args(ctx, width, height, A) != MRP_OK) { ctx->err = "mrp_render: bad image size"; return MRP_E_ARG; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     const int per_block = mrpr::RBLOCK * mrpr::RPPT;
     dim3 grid((unsigned)((width * height + per_block - 1) / per_block), (unsigned)n);
     env_ops(ctx->env_id)->render(ctx->stream, grid, ctx->d_state, d_lanes, ctx->n_lanes, width, height, A, d_rgb);
-    HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipGetLastError());
     return MRP_OK;
 }
 
@@ -675,7 +647,7 @@ int mrp_render(mrp_ctx* ctx, const int32_t* lanes, int n, int width, int height,
     if (!ctx || !lanes || !rgb || n <= 0 || width <= 0 || height <= 0) return MRP_E_ARG;
     for (int i = 0; i < n; ++i)
         if (lanes[i] < 0 || lanes[i] >= ctx->n_lanes) { ctx->err = "mrp_render: lane index out of range"; return MRP_E_ARG; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     Scoped<int32_t> dl;
     Scoped<uint8_t> dimg;
     const size_t img = (size_t)n * width * height * 3;
@@ -711,11 +683,11 @@ int mrp_pixels_device(mrp_ctx* ctx, int width, int height, int channels, int dep
     mrpr::RenderArgs A;
     const int rc = pixels_args(ctx, width, height, channels, depth, d_prev, d_next, A);
     if (rc != MRP_OK) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     dim3 grid((unsigned)ctx->n_lanes, (unsigned)((width * height + mrpr::PIX_CHUNK - 1) / mrpr::PIX_CHUNK));
     env_ops(ctx->env_id)->pixels(ctx->stream, grid, ctx->d_state, ctx->n_lanes, width, height, channels, depth, A, d_done,
                                  d_prev, d_next);
-    HIPCHK(ctx, hipGetLastError());
+    MRP_HIPCHK(ctx, hipGetLastError());
     return MRP_OK;
 }
 
@@ -724,7 +696,7 @@ int mrp_pixels(mrp_ctx* ctx, int width, int height, int channels, int depth, con
     mrpr::RenderArgs A;
     int rc = pixels_args(ctx, width, height, channels, depth, prev, next, A);
     if (rc != MRP_OK) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nl = (size_t)ctx->n_lanes, bytes = nl * depth * width * height * channels;
     Scoped<uint8_t> dd, dp, dn;   // dd / dp stay null where the caller passes no done bytes / no earlier stack
     rc = MRP_E_HIP;
@@ -745,7 +717,7 @@ int mrp_pixels(mrp_ctx* ctx, int width, int height, int channels, int depth, con
 
 int mrp_get_goals(mrp_ctx* ctx, double* out) {
     if (!ctx || !out) return MRP_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    MRP_HIPCHK(ctx, hipSetDevice(ctx->device));
     Scoped<double> d;
     const size_t bytes = (size_t)ctx->n_lanes * ctx->n_blocks * 3 * sizeof(double);
     hipError_t e = d.alloc(bytes);
@@ -776,19 +748,10 @@ int mrp_shapes(int env_id, int32_t* n_fix, int32_t* fix_body, int32_t* counts, f
 }
 
 int mrp_selftest_sincos(int device, const float* x, float* sin_out, float* cos_out, int n) {
-    if (!x || !sin_out || !cos_out || n <= 0) return MRP_E_ARG;
-    if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
-    Scoped<float> dx, ds, dc;
-    size_t bytes = (size_t)n * sizeof(float);
-    int rc = MRP_E_HIP;
-    if (dx.alloc(bytes) == hipSuccess && ds.alloc(bytes) == hipSuccess && dc.alloc(bytes) == hipSuccess &&
-        hipMemcpy(dx.get(), x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_sincos, dim3((n + 255) / 256), dim3(256), 0, 0, dx.get(), ds.get(), dc.get(), n);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(sin_out, ds.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(cos_out, dc.get(), bytes, hipMemcpyDeviceToHost) == hipSuccess)
-            rc = MRP_OK;
-    }
-    return rc;
+    if (!cos_out) return MRP_E_ARG;
+    return selftest_elementwise(device, x, sin_out, cos_out, n, [](dim3 grid, dim3 block, const float* dx, float* ds, float* dc, int cnt) {
+        hipLaunchKernelGGL(k_sincos, grid, block, 0, 0, dx, ds, dc, cnt);
+    });
 }
 
 }  // extern "C"

@@ -29,6 +29,9 @@
 #include <string>
 
 #include "../../include/mrp.h"
+#include "mrp_host.h"
+
+using namespace mrp_host;
 
 namespace {
 
@@ -258,14 +261,12 @@ struct mrp_norm {
     int n_stats() const { return 2 * obs_dim + 4; }
 };
 
-#define NCHK(n, expr)                                                      \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) {                                            \
-            (n)->err = std::string(#expr) + ": " + hipGetErrorString(_e);  \
-            return MRP_E_HIP;                                              \
-        }                                                                  \
-    } while (0)
+// MRP_E_ARG with a message that names the function; without an object it goes where
+// mrp_norm_last_error(NULL) reads it
+static int norm_bad(mrp_norm* n, const char* what) {
+    (n ? n->err : g_norm_create_error) = what;
+    return MRP_E_ARG;
+}
 
 extern "C" {
 
@@ -285,16 +286,11 @@ void mrp_norm_destroy(mrp_norm* n) {
 int mrp_norm_create(int n_lanes, int obs_dim, int device, double clip_obs, double clip_reward, double gamma, double epsilon,
                     mrp_norm** out) {
     g_norm_create_error.clear();
-    if (!out || n_lanes <= 0 || obs_dim <= 0) { g_norm_create_error = "bad argument"; return MRP_E_ARG; }
+    if (!out || n_lanes <= 0 || obs_dim <= 0) return norm_bad(nullptr, "mrp_norm_create: null out, n_lanes < 1 or obs_dim < 1");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        g_norm_create_error = "no HIP device available (no CPU fallback)";
-        return MRP_E_HIP;
-    }
-    if (device < 0 || device >= ndev) { g_norm_create_error = "device index out of range"; return MRP_E_ARG; }
+    if (const int rc = select_device(device, g_norm_create_error)) return rc;
     mrp_norm* n = new (std::nothrow) mrp_norm();
-    if (!n) { g_norm_create_error = "out of host memory"; return MRP_E_ARG; }
+    if (!n) return norm_bad(nullptr, "mrp_norm_create: out of host memory");
     n->n_lanes = n_lanes; n->obs_dim = obs_dim; n->device = device;
     n->clip_obs = clip_obs; n->clip_rew = clip_reward; n->gamma = gamma; n->eps = epsilon;
     auto fail = [&](const char* what, hipError_t e) {
@@ -327,51 +323,51 @@ int mrp_norm_create(int n_lanes, int obs_dim, int device, double clip_obs, doubl
 }
 
 int mrp_norm_set_stream(mrp_norm* n, void* hip_stream) {
-    if (!n) return MRP_E_ARG;
+    if (!n) return norm_bad(n, "mrp_norm_set_stream: null handle");
     n->stream = (hipStream_t)hip_stream;   // NULL: the HIP null stream (torch's default stream)
     return MRP_OK;
 }
 
 int mrp_norm_set_training(mrp_norm* n, int training) {
-    if (!n) return MRP_E_ARG;
+    if (!n) return norm_bad(n, "mrp_norm_set_training: null handle");
     n->training = training ? 1 : 0;
     return MRP_OK;
 }
 
 int mrp_norm_set_norm_obs(mrp_norm* n, int norm_obs) {
-    if (!n) return MRP_E_ARG;
+    if (!n) return norm_bad(n, "mrp_norm_set_norm_obs: null handle");
     n->norm_obs = norm_obs ? 1 : 0;
     return MRP_OK;
 }
 
 static int norm_launch(mrp_norm* n, const float* obs, const float* reward, const double* reward64, const uint8_t* done,
                        const float* term, float* obs_out, float* reward_out, float* term_out, double* ep_ret_out, int* ep_len_out, int step) {
-    NCHK(n, hipSetDevice(n->device));
+    MRP_HIPCHK(n, hipSetDevice(n->device));
     const int L = n->n_lanes, D = n->obs_dim;
     // SB3 VecNormalize: obs statistics move when training and norm_obs, the returns' when training
     const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
     if (upd_obs || upd_ret) {
         hipLaunchKernelGGL(k_moments, dim3(D + 1), dim3(NT), 0, n->stream, obs, L, D, reward, n->d_returns, n->gamma,
                            n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret);
-        NCHK(n, hipGetLastError());
+        MRP_HIPCHK(n, hipGetLastError());
     }
     const int nthreads = L * D > L ? L * D : L;
     hipLaunchKernelGGL(k_apply, dim3((nthreads + NT - 1) / NT), dim3(NT), 0, n->stream, obs, term, L, D, n->obs_mean(),
                        n->obs_var(), n->obs_count(), upd_obs, n->ret_stats(), n->clip_obs, n->clip_rew, n->eps, reward, reward64,
                        done, n->d_returns, obs_out, term_out, reward_out, n->d_ep_ret, n->d_ep_len, ep_ret_out, ep_len_out, step);
-    NCHK(n, hipGetLastError());
+    MRP_HIPCHK(n, hipGetLastError());
     return MRP_OK;
 }
 
 int mrp_norm_reset_device(mrp_norm* n, const float* d_obs, float* d_obs_out) {
-    if (!n || !d_obs || !d_obs_out) return MRP_E_ARG;
+    if (!n || !d_obs || !d_obs_out) return norm_bad(n, "mrp_norm_reset_device: null pointer");
     return norm_launch(n, d_obs, nullptr, nullptr, nullptr, nullptr, d_obs_out, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 int mrp_norm_step_device_ex(mrp_norm* n, const float* d_obs, const float* d_reward, const double* d_reward64, const uint8_t* d_done,
                             const float* d_term_obs, float* d_obs_out, float* d_reward_out, float* d_term_out, double* d_ep_return,
                             int32_t* d_ep_len) {
-    if (!n || !d_obs || !d_reward || !d_done || !d_obs_out || !d_reward_out) return MRP_E_ARG;
+    if (!n || !d_obs || !d_reward || !d_done || !d_obs_out || !d_reward_out) return norm_bad(n, "mrp_norm_step_device: null pointer");
     return norm_launch(n, d_obs, d_reward, d_reward64, d_done, d_term_obs, d_obs_out, d_reward_out, d_term_out, d_ep_return,
                        d_ep_len, 1);
 }
@@ -383,18 +379,18 @@ int mrp_norm_step_device(mrp_norm* n, const float* d_obs, const float* d_reward,
 }
 
 int mrp_norm_get_stats(mrp_norm* n, double* out) {
-    if (!n || !out) return MRP_E_ARG;
-    NCHK(n, hipSetDevice(n->device));
-    NCHK(n, hipMemcpyAsync(out, n->d_stats, n->n_stats() * sizeof(double), hipMemcpyDeviceToHost, n->stream));
-    NCHK(n, hipStreamSynchronize(n->stream));
+    if (!n || !out) return norm_bad(n, "mrp_norm_get_stats: null pointer");
+    MRP_HIPCHK(n, hipSetDevice(n->device));
+    MRP_HIPCHK(n, hipMemcpyAsync(out, n->d_stats, n->n_stats() * sizeof(double), hipMemcpyDeviceToHost, n->stream));
+    MRP_HIPCHK(n, hipStreamSynchronize(n->stream));
     return MRP_OK;
 }
 
 int mrp_norm_set_stats(mrp_norm* n, const double* in) {
-    if (!n || !in) return MRP_E_ARG;
-    NCHK(n, hipSetDevice(n->device));
-    NCHK(n, hipMemcpyAsync(n->d_stats, in, n->n_stats() * sizeof(double), hipMemcpyHostToDevice, n->stream));
-    NCHK(n, hipStreamSynchronize(n->stream));
+    if (!n || !in) return norm_bad(n, "mrp_norm_set_stats: null pointer");
+    MRP_HIPCHK(n, hipSetDevice(n->device));
+    MRP_HIPCHK(n, hipMemcpyAsync(n->d_stats, in, n->n_stats() * sizeof(double), hipMemcpyHostToDevice, n->stream));
+    MRP_HIPCHK(n, hipStreamSynchronize(n->stream));
     return MRP_OK;
 }
 
@@ -412,16 +408,16 @@ int mrp_gae_device(int device, void* hip_stream, int n_steps, int n_lanes, const
         return bad("null pointer");
     if ((d_truncated == nullptr) != (d_terminal_values == nullptr))
         return bad("d_truncated and d_terminal_values are given together or not at all");
-    const void* ins[] = {d_rewards, d_values, d_episode_starts, d_truncated, d_terminal_values, d_last_values, d_last_dones};
-    for (const void* p : ins)
-        if (p && (p == (const void*)d_advantages || p == (const void*)d_returns)) return bad("an output aliases an input");
-    if (d_advantages == d_returns) return bad("d_advantages and d_returns are the same array");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        err = "no HIP device available (no CPU fallback)";
-        return MRP_E_HIP;
+    // extents in bytes: the flag arrays hold one byte per element
+    const size_t n = (size_t)n_lanes, tn = (size_t)n_steps * n, f = sizeof(float);
+    if (const char* what = check_outputs({{d_rewards, tn * f}, {d_values, tn * f}, {d_episode_starts, tn}, {d_truncated, tn},
+                                          {d_terminal_values, tn * f}, {d_last_values, n * f}, {d_last_dones, n}},
+                                         {{d_advantages, tn * f}, {d_returns, tn * f}}))
+        return bad(what);
+    if (const int rc = select_device(device, err)) {
+        if (rc == MRP_E_ARG) err.insert(0, "mrp_gae_device: ");
+        return rc;
     }
-    if (device < 0 || device >= ndev) return bad("device index out of range");
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) { err = std::string("hipSetDevice: ") + hipGetErrorString(e); return MRP_E_HIP; }
     const float g32 = (float)gamma, c32 = (float)(gamma * gae_lambda);

@@ -26,10 +26,13 @@
 #include <vector>
 
 #include "../../include/mrp.h"
+#include "mrp_host.h"
 #include "mrp_math.h"
+#include "mrp_policy_layout.h"
 #include "mrp_policy_net.h"
 
 using namespace mrp_pol;
+using namespace mrp_host;
 
 namespace {
 
@@ -121,46 +124,14 @@ __global__ void k_tanh(const float* __restrict__ x, float* __restrict__ out, int
 
 thread_local std::string g_policy_create_error;
 
-}  // namespace
-
-namespace {
-
-inline int pad32(int n) { return (n + 31) & ~31; }
-
-// the device image of the parameters: per hidden layer the packed weights [K][Npad] and bias [Npad],
-// then the heads' rows (padded to 4 floats), log_std and std; fills the Net's pointers relative to `base`
-size_t layout(mrp_policy* p, float* base) {
-    Net& n = p->net;
-    size_t off = 0;
-    auto take = [&](size_t count) { float* q = base ? base + off : nullptr; off += (count + 3) & ~(size_t)3; return q; };
-    int li = 0;
-    auto towers = [&](Layer* L, int count, int K) {
-        for (int i = 0; i < count; ++i, ++li) {
-            L[i].K = K; L[i].N = p->widths[li]; L[i].Npad = pad32(L[i].N);
-            L[i].w = take((size_t)K * L[i].Npad);
-            L[i].b = take(L[i].Npad);
-            K = L[i].N;
-        }
-        return K;
-    };
-    const int kt = towers(n.shared, n.n_shared, n.obs_dim);
-    n.act.K = towers(n.pi, n.n_pi, kt);
-    n.val.K = towers(n.vf, n.n_vf, kt);
-    n.act.Kpad = (n.act.K + 3) & ~3; n.val.Kpad = (n.val.K + 3) & ~3;
-    n.act.w = take((size_t)n.act_dim * n.act.Kpad); n.act.b = take(n.act_dim);
-    n.val.w = take(n.val.Kpad); n.val.b = take(1);
-    n.log_std = take(n.act_dim); n.std = take(n.act_dim);
-    return off;
-}
-
 int policy_launch(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, const float* d_eps_in, uint64_t seed,
                   uint64_t lane_offset, uint64_t counter, int deterministic, int values_only, float* d_actions, float* d_clipped,
                   float* d_values, float* d_log_probs, float* d_eps_out) {
-    PCHK(p, hipSetDevice(p->device));
+    MRP_HIPCHK(p, hipSetDevice(p->device));
     const dim3 grid((unsigned)(((long long)n_lanes + P_TILE - 1) / P_TILE)), block(P_NT);
     hipLaunchKernelGGL(k_policy, grid, block, 0, (hipStream_t)hip_stream, p->net, n_lanes, d_obs, d_eps_in, seed, lane_offset,
                        counter, deterministic, values_only, d_actions, d_clipped, d_values, d_log_probs, d_eps_out);
-    PCHK(p, hipGetLastError());
+    MRP_HIPCHK(p, hipGetLastError());
     return MRP_OK;
 }
 
@@ -196,12 +167,10 @@ int mrp_policy_create(int device, int obs_dim, int act_dim, int n_shared, int n_
     if (nl > 0 && !widths) return bad("null widths");
     for (int i = 0; i < nl; ++i)
         if (widths[i] < 1 || widths[i] > P_MAXW) return bad("a layer width outside 1..256");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        err = "no HIP device available (no CPU fallback)";
-        return MRP_E_HIP;
+    if (const int rc = select_device(device, err)) {
+        if (rc == MRP_E_ARG) err.insert(0, "mrp_policy_create: ");
+        return rc;
     }
-    if (device < 0 || device >= ndev) return bad("device index out of range");
     mrp_policy* p = new (std::nothrow) mrp_policy();
     if (!p) return bad("out of host memory");
     p->device = device; p->n_layers = nl;
@@ -217,85 +186,37 @@ int mrp_policy_create(int device, int obs_dim, int act_dim, int n_shared, int n_
         return MRP_E_HIP;
     }
     layout(p, p->d_params);
+    p->map = param_map(*p);
     *out = p;
     return MRP_OK;
 }
 
-int mrp_policy_set_params(mrp_policy* p, const float* const* weights, const float* const* biases, const float* log_std,
-                          const float* std) {
+int mrp_policy_n_params(const mrp_policy* p) { return p ? (int)p->map.size() : MRP_E_ARG; }
+
+int mrp_policy_set_params(mrp_policy* p, const float* flat, const float* std) {
     if (!p) return MRP_E_ARG;
-    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_set_params: ") + what; return MRP_E_ARG; };
-    if (!weights || !biases || !log_std || !std) return bad("null pointer");
-    for (int i = 0; i < p->n_layers + 2; ++i)
-        if (!weights[i] || !biases[i]) return bad("null layer pointer");
-    const Net& n = p->net;
-    std::vector<float> h(p->n_floats, 0.0f);
-    float* d0 = p->d_params;
-    auto at = [&](const float* dev) { return h.data() + (dev - d0); };
-    int li = 0;
-    auto pack = [&](const Layer* L, int count) {
-        for (int i = 0; i < count; ++i, ++li) {
-            float* w = at(L[i].w);
-            float* b = at(L[i].b);
-            for (int j = 0; j < L[i].N; ++j) {
-                for (int k = 0; k < L[i].K; ++k) w[(size_t)k * L[i].Npad + j] = weights[li][(size_t)j * L[i].K + k];
-                b[j] = biases[li][j];
-            }
-        }
-    };
-    pack(n.shared, n.n_shared); pack(n.pi, n.n_pi); pack(n.vf, n.n_vf);
-    for (int o = 0; o < n.act_dim; ++o)
-        for (int k = 0; k < n.act.K; ++k) at(n.act.w)[(size_t)o * n.act.Kpad + k] = weights[li][(size_t)o * n.act.K + k];
-    for (int e = 0; e < n.val.K; ++e) at(n.val.w)[e] = weights[li + 1][e];
-    for (int i = 0; i < n.act_dim; ++i) {
-        at(n.act.b)[i] = biases[li][i];
-        at(n.log_std)[i] = log_std[i];
-        at(n.std)[i] = std[i];
-    }
-    at(n.val.b)[0] = biases[li + 1][0];
-    PCHK(p, hipSetDevice(p->device));
-    PCHK(p, hipDeviceSynchronize());   // no launch still reads the old parameters
-    PCHK(p, hipMemcpy(p->d_params, h.data(), p->n_floats * sizeof(float), hipMemcpyHostToDevice));
+    if (!flat || !std) { p->err = "mrp_policy_set_params: null pointer"; return MRP_E_ARG; }
+    std::vector<float> h(p->n_floats, 0.0f);   // the pad columns and pad rows stay zero
+    for (size_t e = 0; e < p->map.size(); ++e) h[p->map[e].image] = flat[e];
+    for (int i = 0; i < p->net.act_dim; ++i) h[(p->net.std - p->d_params) + i] = std[i];
+    MRP_HIPCHK(p, hipSetDevice(p->device));
+    MRP_HIPCHK(p, hipDeviceSynchronize());   // no launch still reads the old parameters
+    MRP_HIPCHK(p, hipMemcpy(p->d_params, h.data(), p->n_floats * sizeof(float), hipMemcpyHostToDevice));
     p->ready = 1;
     ++p->version;
     return MRP_OK;
 }
 
-int mrp_policy_get_params(mrp_policy* p, float* const* weights, float* const* biases, float* log_std, float* std) {
+int mrp_policy_get_params(mrp_policy* p, float* flat, float* std) {
     if (!p) return MRP_E_ARG;
-    auto bad = [&](const char* what) { p->err = std::string("mrp_policy_get_params: ") + what; return MRP_E_ARG; };
-    if (!weights || !biases || !log_std || !std) return bad("null pointer");
-    for (int i = 0; i < p->n_layers + 2; ++i)
-        if (!weights[i] || !biases[i]) return bad("null layer pointer");
+    if (!flat || !std) { p->err = "mrp_policy_get_params: null pointer"; return MRP_E_ARG; }
     if (!p->ready) { p->err = "mrp_policy_get_params: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
-    const Net& n = p->net;
     std::vector<float> h(p->n_floats);
-    PCHK(p, hipSetDevice(p->device));
-    PCHK(p, hipDeviceSynchronize());   // every launch that writes the parameters has finished
-    PCHK(p, hipMemcpy(h.data(), p->d_params, p->n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    const float* d0 = p->d_params;
-    auto at = [&](const float* dev) { return h.data() + (dev - d0); };
-    int li = 0;
-    auto unpack = [&](const Layer* L, int count) {
-        for (int i = 0; i < count; ++i, ++li) {
-            const float* w = at(L[i].w);
-            const float* b = at(L[i].b);
-            for (int j = 0; j < L[i].N; ++j) {
-                for (int k = 0; k < L[i].K; ++k) weights[li][(size_t)j * L[i].K + k] = w[(size_t)k * L[i].Npad + j];
-                biases[li][j] = b[j];
-            }
-        }
-    };
-    unpack(n.shared, n.n_shared); unpack(n.pi, n.n_pi); unpack(n.vf, n.n_vf);
-    for (int o = 0; o < n.act_dim; ++o)
-        for (int k = 0; k < n.act.K; ++k) weights[li][(size_t)o * n.act.K + k] = at(n.act.w)[(size_t)o * n.act.Kpad + k];
-    for (int e = 0; e < n.val.K; ++e) weights[li + 1][e] = at(n.val.w)[e];
-    for (int i = 0; i < n.act_dim; ++i) {
-        biases[li][i] = at(n.act.b)[i];
-        log_std[i] = at(n.log_std)[i];
-        std[i] = at(n.std)[i];
-    }
-    biases[li + 1][0] = at(n.val.b)[0];
+    MRP_HIPCHK(p, hipSetDevice(p->device));
+    MRP_HIPCHK(p, hipDeviceSynchronize());   // every launch that writes the parameters has finished
+    MRP_HIPCHK(p, hipMemcpy(h.data(), p->d_params, p->n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < p->map.size(); ++e) flat[e] = h[p->map[e].image];
+    for (int i = 0; i < p->net.act_dim; ++i) std[i] = h[(p->net.std - p->d_params) + i];
     return MRP_OK;
 }
 
@@ -306,13 +227,10 @@ int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const fl
     auto bad = [&](const char* what) { p->err = std::string("mrp_policy_act_device: ") + what; return MRP_E_ARG; };
     if (n_lanes < 1) return bad("n_lanes < 1");
     if (!d_obs || !d_actions) return bad("null pointer");
-    float* outs[] = {d_actions, d_clipped, d_values, d_log_probs, d_eps_out};
-    for (int i = 0; i < 5; ++i) {
-        if (!outs[i]) continue;
-        if (outs[i] == d_obs || outs[i] == d_eps_in) return bad("an output aliases an input");
-        for (int j = 0; j < i; ++j)
-            if (outs[i] == outs[j]) return bad("two outputs are the same array");
-    }
+    const size_t n = (size_t)n_lanes * sizeof(float), nO = n * p->net.obs_dim, nA = n * p->net.act_dim;
+    if (const char* what = check_outputs({{d_obs, nO}, {d_eps_in, nA}},
+                                         {{d_actions, nA}, {d_clipped, nA}, {d_values, n}, {d_log_probs, n}, {d_eps_out, nA}}))
+        return bad(what);
     if (!p->ready) { p->err = "mrp_policy_act_device: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
     return policy_launch(p, hip_stream, n_lanes, d_obs, d_eps_in, seed, lane_offset, counter, deterministic ? 1 : 0, 0, d_actions,
                          d_clipped, d_values, d_log_probs, d_eps_out);
@@ -323,25 +241,16 @@ int mrp_policy_values_device(mrp_policy* p, void* hip_stream, int n_lanes, const
     auto bad = [&](const char* what) { p->err = std::string("mrp_policy_values_device: ") + what; return MRP_E_ARG; };
     if (n_lanes < 1) return bad("n_lanes < 1");
     if (!d_obs || !d_values) return bad("null pointer");
-    if (d_values == d_obs) return bad("the output aliases the input");
+    const size_t n = (size_t)n_lanes * sizeof(float);
+    if (const char* what = check_outputs({{d_obs, n * p->net.obs_dim}}, {{d_values, n}})) return bad(what);
     if (!p->ready) { p->err = "mrp_policy_values_device: no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
     return policy_launch(p, hip_stream, n_lanes, d_obs, nullptr, 0, 0, 0, 1, 1, nullptr, nullptr, d_values, nullptr, nullptr);
 }
 
 int mrp_selftest_tanh(int device, const float* x, float* out, int n) {
-    if (!x || !out || n <= 0) return MRP_E_ARG;
-    if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
-    float *dx = nullptr, *dy = nullptr;
-    const size_t bytes = (size_t)n * sizeof(float);
-    int rc = MRP_E_HIP;
-    if (hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&dy, bytes) == hipSuccess &&
-        hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_tanh, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = MRP_OK;
-    }
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    return rc;
+    return selftest_elementwise(device, x, out, nullptr, n, [](dim3 grid, dim3 block, const float* dx, float* dy, float*, int cnt) {
+        hipLaunchKernelGGL(k_tanh, grid, block, 0, 0, dx, dy, cnt);
+    });
 }
 
 }  // extern "C"

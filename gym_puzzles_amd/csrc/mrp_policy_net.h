@@ -1,11 +1,9 @@
 // mrp_policy_net.h -- what the device policy's forward kernel (mrp_policy.hip) and the PPO update
-// (mrp_ppo.hip) share: the Net the kernels take by value, the policy object, and the device code of a
-// hidden layer (v_mfma_f32_32x32x2_f32 over activations in LDS) and of a narrow head.  See
-// mrp_policy.hip for the kernel shape and the lane maps.
+// (mrp_ppo.hip) share: the Net the kernels take by value and the device code of a hidden layer
+// (v_mfma_f32_32x32x2_f32 over activations in LDS) and of a narrow head.  See mrp_policy.hip for the
+// kernel shape and the lane maps, mrp_policy_layout.h for the policy object and its parameter map.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#include <string>
 
 #include "../../include/mrp.h"
 #include "mrp_math.h"
@@ -129,22 +127,3 @@ static __device__ __forceinline__ void head(const Head& H, int n_out, const floa
 }
 
 }  // namespace mrp_pol
-
-struct mrp_policy {
-    int device = 0, ready = 0, n_layers = 0;
-    int version = 0;                 // counts mrp_policy_set_params calls: mrp_ppo re-imports its master copy when it moves
-    int widths[3 * mrp_pol::P_MAXL] = {};
-    mrp_pol::Net net = {};
-    float* d_params = nullptr;
-    size_t n_floats = 0;
-    std::string err;
-};
-
-#define PCHK(p, expr)                                                      \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) {                                            \
-            (p)->err = std::string(#expr) + ": " + hipGetErrorString(_e);  \
-            return MRP_E_HIP;                                              \
-        }                                                                  \
-    } while (0)

@@ -30,10 +30,13 @@
 #include <vector>
 
 #include "../../include/mrp.h"
+#include "mrp_host.h"
 #include "mrp_math.h"
+#include "mrp_policy_layout.h"
 #include "mrp_policy_net.h"
 
 using namespace mrp_pol;
+using namespace mrp_host;
 
 namespace {
 
@@ -389,8 +392,6 @@ __global__ void k_exp(const float* __restrict__ x, float* __restrict__ out, int 
 
 thread_local std::string g_ppo_create_error;
 
-inline int pad32(int n) { return (n + 31) & ~31; }
-
 }  // namespace
 
 struct mrp_ppo {
@@ -423,23 +424,14 @@ int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const fl
     if (B < 1) return bad("B < 1");
     if (B > o->max_batch) return bad("B > max_batch");
     if (!obs || !actions || !old_lp || !adv || !ret || !d_stats) return bad("null pointer");
-    // the arrays' extents are known, so an output that overlaps an input anywhere (a view into the same
-    // allocation at an offset) is refused, not only one that starts at the same address
-    const size_t nB = (size_t)B;
-    const float* ins[] = {obs, actions, old_lp, adv, ret};
-    const size_t in_n[] = {nB * o->pn.net.obs_dim, nB * o->pn.net.act_dim, nB, nB, nB};
-    auto overlap = [](const float* a, size_t na, const float* b, size_t nb) {
-        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-        return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
-    };
-    for (int i = 0; i < 5; ++i) {
-        if (overlap(d_stats, NSTAT, ins[i], in_n[i]) || (d_grad && overlap(d_grad, (size_t)o->n_params, ins[i], in_n[i])))
-            return bad("an output aliases an input");
-    }
-    if (d_grad && overlap(d_grad, (size_t)o->n_params, d_stats, NSTAT)) return bad("the two outputs overlap");
+    const size_t f = sizeof(float), nB = (size_t)B * f;   // d_grad is null in a step: the object's own vector
+    if (const char* what = check_outputs(
+            {{obs, nB * o->pn.net.obs_dim}, {actions, nB * o->pn.net.act_dim}, {old_lp, nB}, {adv, nB}, {ret, nB}},
+            {{d_stats, NSTAT * f}, {d_grad, (size_t)o->n_params * f}}))
+        return bad(what);
     mrp_policy* p = o->policy;
     if (!p->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
-    PCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipSetDevice(o->device));
     const int P = o->n_params, pb = (P + P_NT - 1) / P_NT;
     if (o->seen_version != p->version) {
         hipLaunchKernelGGL(k_ppo_import, dim3(pb), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P, o->param(), o->d_rows);
@@ -456,7 +448,7 @@ int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const fl
     float* g = d_grad ? d_grad : o->grad();
     hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g);
     hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats);
-    PCHK(o, hipGetLastError());
+    MRP_HIPCHK(o, hipGetLastError());
     return MRP_OK;
 }
 
@@ -466,7 +458,7 @@ extern "C" {
 
 const char* mrp_ppo_last_error(const mrp_ppo* o) { return o ? o->err.c_str() : g_ppo_create_error.c_str(); }
 
-int mrp_ppo_n_params(const mrp_ppo* o) { return o ? o->n_params : MRP_E_ARG; }
+int mrp_ppo_n_params(const mrp_ppo* o) { return o ? o->n_params : MRP_E_ARG; }   // mrp_policy_n_params of its policy
 
 void mrp_ppo_destroy(mrp_ppo* o) {
     if (!o) return;
@@ -494,42 +486,28 @@ int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out) {
     PpoNet& pn = o->pn;
     pn.net = net;
     const int S = net.n_shared, NP = net.n_pi, NV = net.n_vf, nl = S + NP + NV, A = net.act_dim, D = net.obs_dim;
-    const float* image = policy->d_params;
     std::vector<const Layer*> layers;
     for (int i = 0; i < S; ++i) layers.push_back(&net.shared[i]);
     for (int i = 0; i < NP; ++i) layers.push_back(&net.pi[i]);
     for (int i = 0; i < NV; ++i) layers.push_back(&net.vf[i]);
     // the input of hidden layer li: -1 the observations, else a layer index
     auto input_of = [&](int li) { return li == 0 ? -1 : (li == S || li == S + NP) ? S - 1 : li - 1; };
-    // flat order: log_std, then per layer weight [out][in] and bias; the two image indices of every element
-    std::vector<int> fwd, row;
-    std::vector<int> w_off(nl + 2), b_off(nl + 2);
-    for (int i = 0; i < A; ++i) { fwd.push_back((int)(net.log_std - image) + i); row.push_back(-1); }
+    // the row-major image [N][pad32(K)] of every hidden layer's weights, one behind the other
     size_t rows_floats = 0;
     std::vector<size_t> rows_at(nl);
-    for (int li = 0; li < nl; ++li) {
-        const Layer& L = *layers[li];
-        rows_at[li] = rows_floats;
-        const int Kpad = pad32(L.K);
-        w_off[li] = (int)fwd.size();
-        for (int j = 0; j < L.N; ++j)
-            for (int k = 0; k < L.K; ++k) {
-                fwd.push_back((int)(L.w - image) + k * L.Npad + j);
-                row.push_back((int)(rows_floats + (size_t)j * Kpad + k));
-            }
-        b_off[li] = (int)fwd.size();
-        for (int j = 0; j < L.N; ++j) { fwd.push_back((int)(L.b - image) + j); row.push_back(-1); }
-        rows_floats += (size_t)L.N * Kpad;
+    for (int li = 0; li < nl; ++li) { rows_at[li] = rows_floats; rows_floats += (size_t)layers[li]->N * pad32(layers[li]->K); }
+    // one walk of the policy's parameter map (flat order): the two image indices of every element, and where
+    // each layer's weight and bias begin in the flat vector
+    std::vector<int> fwd, row;
+    std::vector<int> w_off(nl + 2), b_off(nl + 2);
+    for (const ParamRef& r : policy->map) {
+        const bool hidden_weight = r.slot >= 0 && r.slot < nl && r.k >= 0;
+        const int flat = (int)fwd.size();
+        if (r.slot >= 0 && r.j == 0 && r.k == 0) w_off[r.slot] = flat;
+        if (r.slot >= 0 && r.j == 0 && r.k < 0) b_off[r.slot] = flat;
+        fwd.push_back(r.image);
+        row.push_back(hidden_weight ? (int)(rows_at[r.slot] + (size_t)r.j * pad32(layers[r.slot]->K) + r.k) : -1);
     }
-    w_off[nl] = (int)fwd.size();
-    for (int i = 0; i < A; ++i)
-        for (int k = 0; k < net.act.K; ++k) { fwd.push_back((int)(net.act.w - image) + i * net.act.Kpad + k); row.push_back(-1); }
-    b_off[nl] = (int)fwd.size();
-    for (int i = 0; i < A; ++i) { fwd.push_back((int)(net.act.b - image) + i); row.push_back(-1); }
-    w_off[nl + 1] = (int)fwd.size();
-    for (int k = 0; k < net.val.K; ++k) { fwd.push_back((int)(net.val.w - image) + k); row.push_back(-1); }
-    b_off[nl + 1] = (int)fwd.size();
-    fwd.push_back((int)(net.val.b - image)); row.push_back(-1);
     const int P = o->n_params = (int)fwd.size();
     // the workspace: activations and deltas per hidden layer, the heads' deltas, the log_std and statistics terms
     size_t ws = 0;
@@ -621,34 +599,24 @@ int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs,
     hipLaunchKernelGGL(k_ppo_adam, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, (hipStream_t)hip_stream, P, p->net.act_dim, o->grad(),
                        o->coef(), o->param(), o->m(), o->v(), o->d_idx, o->d_idx + P, p->d_params, o->d_rows,
                        const_cast<float*>(p->net.std), k);
-    PCHK(o, hipGetLastError());
+    MRP_HIPCHK(o, hipGetLastError());
     return MRP_OK;
 }
 
 int mrp_ppo_get_state(mrp_ppo* o, float* m, float* v) {
     if (!o) return MRP_E_ARG;
     if (!m || !v) { o->err = "mrp_ppo_get_state: null pointer"; return MRP_E_ARG; }
-    PCHK(o, hipSetDevice(o->device));
-    PCHK(o, hipDeviceSynchronize());
-    PCHK(o, hipMemcpy(m, o->m(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
-    PCHK(o, hipMemcpy(v, o->v(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipDeviceSynchronize());
+    MRP_HIPCHK(o, hipMemcpy(m, o->m(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    MRP_HIPCHK(o, hipMemcpy(v, o->v(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
     return MRP_OK;
 }
 
 int mrp_selftest_exp(int device, const float* x, float* out, int n) {
-    if (!x || !out || n <= 0) return MRP_E_ARG;
-    if (hipSetDevice(device) != hipSuccess) return MRP_E_HIP;
-    float *dx = nullptr, *dy = nullptr;
-    const size_t bytes = (size_t)n * sizeof(float);
-    int rc = MRP_E_HIP;
-    if (hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&dy, bytes) == hipSuccess &&
-        hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess) {
-        hipLaunchKernelGGL(k_exp, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n);
-        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = MRP_OK;
-    }
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    return rc;
+    return selftest_elementwise(device, x, out, nullptr, n, [](dim3 grid, dim3 block, const float* dx, float* dy, float*, int cnt) {
+        hipLaunchKernelGGL(k_exp, grid, block, 0, 0, dx, dy, cnt);
+    });
 }
 
 }  // extern "C"

@@ -29,6 +29,8 @@ import re
 
 import numpy as np
 
+from ._device import Handle, check_tensor, index_of, ptr, stream_of
+
 MAX_WIDTH, MAX_ACT, MAX_DEPTH = 256, 16, 4
 ACTIVATIONS = {"tanh": 0, "relu": 1}        # include/mrp.h MRP_POLICY_TANH / MRP_POLICY_RELU
 LOG_SQRT_2PI = np.float32(0.9189385332046727)
@@ -224,19 +226,50 @@ def policy_ref(params, obs, eps=None, deterministic=False):
     return actions.astype(_f32), clipped.astype(_f32), values, log_probs
 
 
+# ---- flat parameter order ----------------------------------------------------------------------------
+def _layers(params):
+    return params.shared + params.pi + params.vf + [params.action, params.value]
+
+
+def flatten_params(params):
+    """The flat float32 vector of SB3's ``parameters()`` order: ``log_std``, then every layer's
+    ``weight`` (row-major ``[out][in]``) and ``bias`` -- trunk, policy tower, value tower, heads."""
+    parts = [params.log_std]
+    for w, b in _layers(params):
+        parts += [w.ravel(), b]
+    return np.concatenate(parts).astype(_f32)
+
+
+def unflatten_params(like, flat, std=None):
+    """``PolicyParams`` of ``like``'s architecture from a flat vector (``std``: see ``PolicyParams``)."""
+    flat = np.ascontiguousarray(flat, _f32)
+    pos = [like.act_dim]
+
+    def take(shape):
+        n = int(np.prod(shape))
+        out = flat[pos[0]:pos[0] + n].reshape(shape).copy()
+        pos[0] += n
+        return out
+    layers = [(take(w.shape), take(b.shape)) for w, b in _layers(like)]
+    S, Pn = len(like.shared), len(like.pi)
+    nl = S + Pn + len(like.vf)
+    return PolicyParams(layers[:S], layers[S:S + Pn], layers[S + Pn:nl], layers[nl], layers[nl + 1],
+                        flat[:like.act_dim].copy(), like.activation, std=std)
+
+
+def state_dict_from_params(params):
+    """Arrays under SB3's parameter names: the inverse of ``params_from_state_dict``."""
+    sd = {"log_std": params.log_std.copy()}
+    for name, tower in (("shared_net", params.shared), ("policy_net", params.pi), ("value_net", params.vf)):
+        for i, (w, b) in enumerate(tower):     # Linear modules sit at the even indices, activations between them
+            sd[f"mlp_extractor.{name}.{2 * i}.weight"], sd[f"mlp_extractor.{name}.{2 * i}.bias"] = w.copy(), b.copy()
+    for name, (w, b) in (("action_net", params.action), ("value_net", params.value)):
+        sd[f"{name}.weight"], sd[f"{name}.bias"] = w.copy(), b.copy()
+    return sd
+
+
 # ---- the device class --------------------------------------------------------------------------------
-def _check(name, t, dev, dtype, shape):
-    if not t.is_cuda or t.device != dev:
-        raise ValueError(f"DevicePolicy: {name} is on {t.device}, expected {dev}")
-    if t.dtype != dtype:
-        raise ValueError(f"DevicePolicy: {name} is {t.dtype}, expected {dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"DevicePolicy: {name} is {tuple(t.shape)}, expected {tuple(shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"DevicePolicy: {name} is not contiguous")
-
-
-class DevicePolicy:
+class DevicePolicy(Handle):
     """``policy_ref`` on the device, one launch per ``act`` / ``values`` call, bit for bit.
 
     ``from_state_dict`` loads an SB3 ``state_dict``, ``from_arrays`` plain numpy arrays; ``DevicePolicy(
@@ -245,10 +278,10 @@ class DevicePolicy:
     keyed by ``(seed, lane_offset + lane, counter)``; ``counter`` advances with every sampling ``act``
     that draws its own noise."""
 
+    _DESTROY, _LAST_ERROR, _VALUE_ERRORS = "mrp_policy_destroy", "mrp_policy_last_error", (-1, -3)
+
     def __init__(self, obs_dim, act_dim, n_shared, n_pi, n_vf, widths, activation="tanh", device=0, seed=0, lane_offset=0):
         import torch
-
-        from ._native import MrpError, load
         widths = [int(w) for w in widths]
         if activation not in ACTIVATIONS:
             raise ValueError(f"policy: activation {activation!r} is neither 'tanh' nor 'relu'")
@@ -258,16 +291,10 @@ class DevicePolicy:
         self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
         self.seed, self.lane_offset, self.counter = int(seed), int(lane_offset), 0
         self.params = None
-        self._L, self._err = load(), MrpError
-        h = ctypes.c_void_p()
-        index = torch.cuda.current_device() if self.device.index is None else self.device.index
         warr = (ctypes.c_int * max(1, len(widths)))(*widths)
-        rc = self._L.mrp_policy_create(index, self.obs_dim, self.act_dim, n_shared, n_pi, n_vf, warr,
-                                       ACTIVATIONS[activation], ctypes.byref(h))
-        if rc != 0:
-            msg = self._L.mrp_policy_last_error(None).decode()
-            raise (ValueError if rc == -1 else MrpError)(f"mrp_policy_create failed ({rc}): {msg}")
-        self._h = h
+        self._open("mrp_policy_create", index_of(self.device), self.obs_dim, self.act_dim, n_shared, n_pi, n_vf, warr,
+                   ACTIVATIONS[activation])
+        self.n_params = int(self._L.mrp_policy_n_params(self._h))
 
     @classmethod
     def from_params(cls, params, device=0, seed=0, lane_offset=0):
@@ -287,22 +314,13 @@ class DevicePolicy:
         the two heads' ``(weight, bias)`` (see ``PolicyParams``)."""
         return cls.from_params(PolicyParams(shared, pi, vf, action, value, log_std, activation), device, seed, lane_offset)
 
-    def _check_rc(self, rc):
-        if rc == -1 or rc == -3:
-            raise ValueError(self._L.mrp_policy_last_error(self._h).decode())
-        if rc != 0:
-            raise self._err(self._L.mrp_policy_last_error(self._h).decode())
-
     def set_params(self, params) -> None:
         """Load a ``PolicyParams`` of this policy's architecture (synchronises the device)."""
         if ((params.obs_dim, params.act_dim, (len(params.shared), len(params.pi), len(params.vf)), params.widths, params.activation)
                 != (self.obs_dim, self.act_dim, tuple(self.arch), self.widths, self.activation)):
             raise ValueError("DevicePolicy.set_params: the parameters belong to another architecture")
-        layers = params.shared + params.pi + params.vf + [params.action, params.value]
-        n = len(layers)
-        ws = (ctypes.c_void_p * n)(*[w.ctypes.data for w, _ in layers])
-        bs = (ctypes.c_void_p * n)(*[b.ctypes.data for _, b in layers])
-        self._check_rc(self._L.mrp_policy_set_params(self._h, ws, bs, params.log_std.ctypes.data, params.std.ctypes.data))
+        flat = flatten_params(params)
+        self._check_rc(self._L.mrp_policy_set_params(self._h, flat.ctypes.data, params.std.ctypes.data))
         self.params = params
 
     def get_params(self):
@@ -310,32 +328,19 @@ class DevicePolicy:
         steps: the inverse of ``set_params`` (synchronises the device)."""
         if self.params is None:
             raise ValueError("DevicePolicy.get_params: no parameters yet (set_params)")
-        S, Pn, V = self.arch
-        kt = self.widths[S - 1] if S else self.obs_dim
-        # a layer's inputs: the observation, the trunk's output at the head of a tower, else the layer before
-        ins = [self.obs_dim if i == 0 and S else kt if i in (S, S + Pn) else self.widths[i - 1] for i in range(len(self.widths))]
-        kp = self.widths[S + Pn - 1] if Pn else kt
-        kv = self.widths[S + Pn + V - 1] if V else kt
-        layers = [(np.zeros((n, k), _f32), np.zeros(n, _f32)) for n, k in zip(self.widths, ins)]
-        layers += [(np.zeros((self.act_dim, kp), _f32), np.zeros(self.act_dim, _f32)), (np.zeros((1, kv), _f32), np.zeros(1, _f32))]
-        log_std, std = np.zeros(self.act_dim, _f32), np.zeros(self.act_dim, _f32)
-        ws = (ctypes.c_void_p * len(layers))(*[w.ctypes.data for w, _ in layers])
-        bs = (ctypes.c_void_p * len(layers))(*[b.ctypes.data for _, b in layers])
-        self._check_rc(self._L.mrp_policy_get_params(self._h, ws, bs, log_std.ctypes.data, std.ctypes.data))
-        nl = len(self.widths)
-        return PolicyParams(layers[:S], layers[S:S + Pn], layers[S + Pn:nl], layers[nl], layers[nl + 1], log_std,
-                            self.activation, std=std)
+        flat, std = np.zeros(self.n_params, _f32), np.zeros(self.act_dim, _f32)
+        self._check_rc(self._L.mrp_policy_get_params(self._h, flat.ctypes.data, std.ctypes.data))
+        return unflatten_params(self.params, flat, std=std)
 
     def state_dict(self):
         """The device's parameters as arrays under SB3's names: the inverse of ``params_from_state_dict``."""
-        from .ppo import state_dict_from_params
         return state_dict_from_params(self.get_params())
 
     def _obs(self, obs):
         import torch
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
             raise ValueError("DevicePolicy: obs must be a [N, obs_dim] CUDA tensor")
-        _check("obs", obs, self.device, torch.float32, (obs.shape[0], self.obs_dim))
+        check_tensor("DevicePolicy", "obs", obs, self.device, torch.float32, (obs.shape[0], self.obs_dim))
         if obs.shape[0] < 1:
             raise ValueError("DevicePolicy: obs holds no lane")
         return int(obs.shape[0])
@@ -345,6 +350,7 @@ class DevicePolicy:
         [N, act_dim] noise (e.g. ``torch.randn``) or None for the device counter RNG, whose counter
         then advances; ``out``: an optional ``(actions, clipped, values, log_probs)`` tuple of
         preallocated tensors, returned as they are; ``eps_out`` optionally receives the noise used.
+        An output whose memory overlaps an input's or another output's anywhere raises ``ValueError``.
         Returns ``(actions [N, A], clipped [N, A], values [N], log_probs [N])``."""
         import torch
         N, A, f32 = self._obs(obs), self.act_dim, torch.float32
@@ -357,10 +363,8 @@ class DevicePolicy:
         named += [("eps", eps, (N, A)), ("eps_out", eps_out, (N, A))]
         for name, t, shape in named:
             if t is not None:
-                _check(name, t, self.device, f32, shape)
-        ptr = (lambda t: None if t is None else ctypes.c_void_p(t.data_ptr()))
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check_rc(self._L.mrp_policy_act_device(self._h, ctypes.c_void_p(stream), N, ptr(obs), ptr(eps), self.seed,
+                check_tensor("DevicePolicy", name, t, self.device, f32, shape)
+        self._check_rc(self._L.mrp_policy_act_device(self._h, stream_of(self.device), N, ptr(obs), ptr(eps), self.seed,
                                                      self.lane_offset, self.counter, int(bool(deterministic)), ptr(out[0]),
                                                      ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(eps_out)))
         if eps is None and not deterministic:
@@ -374,19 +378,6 @@ class DevicePolicy:
         N = self._obs(obs)
         if out is None:
             out = torch.empty(N, dtype=torch.float32, device=self.device)
-        _check("out", out, self.device, torch.float32, (N,))
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check_rc(self._L.mrp_policy_values_device(self._h, ctypes.c_void_p(stream), N, ctypes.c_void_p(obs.data_ptr()),
-                                                        ctypes.c_void_p(out.data_ptr())))
+        check_tensor("DevicePolicy", "out", out, self.device, torch.float32, (N,))
+        self._check_rc(self._L.mrp_policy_values_device(self._h, stream_of(self.device), N, ptr(obs), ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mrp_policy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

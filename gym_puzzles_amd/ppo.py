@@ -47,8 +47,9 @@ import math
 
 import numpy as np
 
-from .policy import _INV_LN2, _LN2_HI, _LN2_LO, _TANH_C, LOG_SQRT_2PI, PolicyParams, _activate, fma32, linear_ref
-from .policy import _check as _policy_check
+from ._device import Handle, check_tensor, ptr, stream_of
+from .policy import (_INV_LN2, _LN2_HI, _LN2_LO, _TANH_C, LOG_SQRT_2PI, PolicyParams, _activate, _layers,  # noqa: F401
+                     flatten_params, fma32, linear_ref, state_dict_from_params, unflatten_params)
 
 _f32, _f64 = np.float32, np.float64
 CHUNK = 256            # samples per partial sum of a parameter gradient (and of a statistic)
@@ -80,48 +81,6 @@ def exp_ref(x):
         p = r + (r * r) * q
         e = (((1023 + n) << 52).view(_f64) * (1.0 + p)).astype(_f32)
     return np.where(nan, ux, e.view(np.uint32)).astype(np.uint32).view(_f32)
-
-
-# ---- flat parameter order ----------------------------------------------------------------------------
-def _layers(params):
-    return params.shared + params.pi + params.vf + [params.action, params.value]
-
-
-def flatten_params(params):
-    """The flat float32 vector of SB3's ``parameters()`` order: ``log_std``, then every layer's
-    ``weight`` (row-major ``[out][in]``) and ``bias`` -- trunk, policy tower, value tower, heads."""
-    parts = [params.log_std]
-    for w, b in _layers(params):
-        parts += [w.ravel(), b]
-    return np.concatenate(parts).astype(_f32)
-
-
-def unflatten_params(like, flat, std=None):
-    """``PolicyParams`` of ``like``'s architecture from a flat vector (``std``: see ``PolicyParams``)."""
-    flat = np.ascontiguousarray(flat, _f32)
-    pos = [like.act_dim]
-
-    def take(shape):
-        n = int(np.prod(shape))
-        out = flat[pos[0]:pos[0] + n].reshape(shape).copy()
-        pos[0] += n
-        return out
-    layers = [(take(w.shape), take(b.shape)) for w, b in _layers(like)]
-    S, Pn = len(like.shared), len(like.pi)
-    nl = S + Pn + len(like.vf)
-    return PolicyParams(layers[:S], layers[S:S + Pn], layers[S + Pn:nl], layers[nl], layers[nl + 1],
-                        flat[:like.act_dim].copy(), like.activation, std=std)
-
-
-def state_dict_from_params(params):
-    """Arrays under SB3's parameter names: the inverse of ``policy.params_from_state_dict``."""
-    sd = {"log_std": params.log_std.copy()}
-    for name, tower in (("shared_net", params.shared), ("policy_net", params.pi), ("value_net", params.vf)):
-        for i, (w, b) in enumerate(tower):     # Linear modules sit at the even indices, activations between them
-            sd[f"mlp_extractor.{name}.{2 * i}.weight"], sd[f"mlp_extractor.{name}.{2 * i}.bias"] = w.copy(), b.copy()
-    for name, (w, b) in (("action_net", params.action), ("value_net", params.value)):
-        sd[f"{name}.weight"], sd[f"{name}.bias"] = w.copy(), b.copy()
-    return sd
 
 
 # ---- the gradient rule -------------------------------------------------------------------------------
@@ -334,44 +293,32 @@ def ppo_train_ref(params, state, data, epochs, batch_size, **hp):
 
 
 # ---- the device class --------------------------------------------------------------------------------
-def _check(name, t, dev, dtype, shape):
-    try:
-        _policy_check(name, t, dev, dtype, shape)
-    except ValueError as e:
-        raise ValueError(str(e).replace("DevicePolicy", "DevicePPO")) from None
-
-
-class DevicePPO:
+class DevicePPO(Handle):
     """The rule on the device: ``grad`` is ``ppo_grad_ref``, ``step`` is ``ppo_step_ref`` written into
     ``policy``'s device parameters in place (the next ``policy.act`` uses them), ``train`` is SB3's
     epoch / minibatch loop over a ``DeviceRolloutBuffer``.  Nothing here synchronises the device; the
     statistics stay in device tensors.  The optimiser state (master parameters, gradient, Adam moments)
     belongs to this object; ``policy.set_params`` afterwards is picked up by the next call and leaves
-    the moments as they are.  ``learning_rate`` is read at every step."""
+    the moments as they are.  ``learning_rate`` is read at every step.  The library reads ``policy``'s
+    handle in every call, so a call after ``policy.close()`` raises ``ValueError``."""
+
+    _DESTROY, _LAST_ERROR, _VALUE_ERRORS = "mrp_ppo_destroy", "mrp_ppo_last_error", (-1, -3)
 
     def __init__(self, policy, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                  max_grad_norm=0.5, normalize_advantage=True, betas=(0.9, 0.999), eps=1e-5, max_batch=None):
-        from ._native import MrpError, load
         self.policy, self.learning_rate, self.n_epochs, self.batch_size = policy, learning_rate, int(n_epochs), int(batch_size)
         self.clip_range, self.ent_coef, self.vf_coef, self.max_grad_norm = clip_range, ent_coef, vf_coef, max_grad_norm
         self.normalize_advantage, self.betas, self.eps = bool(normalize_advantage), tuple(betas), eps
         self.max_batch = int(self.batch_size if max_batch is None else max_batch)
         self.t = 0
         self.device = policy.device
-        self._L, self._err = load(), MrpError
-        h = ctypes.c_void_p()
-        rc = self._L.mrp_ppo_create(policy._h, self.max_batch, ctypes.byref(h))
-        if rc != 0:
-            msg = self._L.mrp_ppo_last_error(None).decode()
-            raise (ValueError if rc in (-1, -3) else MrpError)(f"mrp_ppo_create failed ({rc}): {msg}")
-        self._h = h
-        self.n_params = int(self._L.mrp_ppo_n_params(h))
+        self._open("mrp_ppo_create", policy._h, self.max_batch)
+        self.n_params = int(self._L.mrp_ppo_n_params(self._h))
 
-    def _check_rc(self, rc):
-        if rc == -1 or rc == -3:
-            raise ValueError(self._L.mrp_ppo_last_error(self._h).decode())
-        if rc != 0:
-            raise self._err(self._L.mrp_ppo_last_error(self._h).decode())
+    @property
+    def _h(self):
+        self.policy._h     # mrp_ppo reads the policy's handle in every call: ValueError once that is closed
+        return super()._h
 
     def _batch(self, obs, actions, old_log_probs, advantages, returns):
         import torch
@@ -383,23 +330,17 @@ class DevicePPO:
         named = (("obs", obs, (B, self.policy.obs_dim)), ("actions", actions, (B, self.policy.act_dim)),
                  ("old_log_probs", old_log_probs, (B,)), ("advantages", advantages, (B,)), ("returns", returns, (B,)))
         for name, t, shape in named:
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"DevicePPO: {name} is not a tensor")
-            _check(name, t, self.device, f32, shape)
+            check_tensor("DevicePPO", name, t, self.device, f32, shape)
         if B > self.max_batch:
             raise ValueError(f"DevicePPO: a minibatch of {B} samples, max_batch is {self.max_batch}")
-        return B, [ctypes.c_void_p(t.data_ptr()) for _, t, _ in named]
+        return B, [ptr(t) for _, t, _ in named]
 
     def _out(self, name, t, n):
         import torch
         if t is None:
             return torch.empty(n, dtype=torch.float32, device=self.device)
-        _check(name, t, self.device, torch.float32, (n,))
+        check_tensor("DevicePPO", name, t, self.device, torch.float32, (n,))
         return t
-
-    def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def grad(self, obs, actions, old_log_probs, advantages, returns, out=None, stats_out=None):
         """``ppo_grad_ref`` on the device: returns ``(flat_grad [n_params], stats [5])`` device
@@ -408,9 +349,8 @@ class DevicePPO:
         B, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns)
         g, st = self._out("out", out, self.n_params), self._out("stats_out", stats_out, 5)
         f = ctypes.c_float
-        self._check_rc(self._L.mrp_ppo_grad_device(self._h, self._stream(), B, *ptrs, f(self.clip_range), f(self.ent_coef),
-                                                   ctypes.c_double(self.vf_coef), ctypes.c_void_p(g.data_ptr()),
-                                                   ctypes.c_void_p(st.data_ptr())))
+        self._check_rc(self._L.mrp_ppo_grad_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
+                                                   ctypes.c_double(self.vf_coef), ptr(g), ptr(st)))
         return g, st
 
     def step(self, obs, actions, old_log_probs, advantages, returns, stats_out=None):
@@ -419,9 +359,9 @@ class DevicePPO:
         st = self._out("stats_out", stats_out, 5)
         sc = adam_scalars(self.t + 1, self.learning_rate, self.betas, self.eps)
         f = ctypes.c_float
-        self._check_rc(self._L.mrp_ppo_step_device(self._h, self._stream(), B, *ptrs, f(self.clip_range), f(self.ent_coef),
+        self._check_rc(self._L.mrp_ppo_step_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
                                                    ctypes.c_double(self.vf_coef), ctypes.c_double(self.max_grad_norm),
-                                                   *[f(float(x)) for x in sc], ctypes.c_void_p(st.data_ptr())))
+                                                   *[f(float(x)) for x in sc], ptr(st)))
         self.t += 1
         return st
 
@@ -448,14 +388,3 @@ class DevicePPO:
         m, v = np.zeros(self.n_params, _f32), np.zeros(self.n_params, _f32)
         self._check_rc(self._L.mrp_ppo_get_state(self._h, m.ctypes.data, v.ctypes.data))
         return m, v
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mrp_ppo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

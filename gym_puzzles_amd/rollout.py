@@ -15,9 +15,9 @@ This module is pure numpy at import; ``gae_device`` and ``DeviceRolloutBuffer`` 
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
+
+from ._device import check_tensor, index_of, ptr, stream_of
 
 
 def gae_ref(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, truncated=None, terminal_values=None):
@@ -55,24 +55,13 @@ def gae_ref(rewards, values, episode_starts, last_values, dones, gamma, gae_lamb
     return adv, adv + values
 
 
-def _check(name, t, dev, dtype, shape):
-    if not t.is_cuda or t.device != dev:
-        raise ValueError(f"gae_device: {name} is on {t.device}, expected {dev}")
-    if t.dtype != dtype:
-        raise ValueError(f"gae_device: {name} is {t.dtype}, expected {dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"gae_device: {name} is {tuple(t.shape)}, expected {tuple(shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"gae_device: {name} is not contiguous")
-
-
 def gae_device(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, truncated=None, terminal_values=None,
                advantages=None, returns=None):
     """``gae_ref`` on the device in one launch (``mrp_gae_device``), bit for bit.  Contiguous CUDA
     tensors on one device: float32 [T, N] rewards / values / terminal_values, uint8 [T, N]
     episode_starts / truncated, float32 [N] last_values, uint8 [N] dones; ``truncated`` and
     ``terminal_values`` come together or not at all.  ``advantages`` / ``returns`` (float32 [T, N],
-    allocated when omitted) may alias no input and not each other.  Asynchronous on the current torch
+    allocated when omitted) may overlap no input and not each other.  Asynchronous on the current torch
     stream of the tensors' device.  Returns ``(advantages, returns)``."""
     import torch
 
@@ -95,12 +84,9 @@ def gae_device(rewards, values, episode_starts, last_values, dones, gamma, gae_l
                                ("terminal_values", terminal_values, f32, (T, N)), ("advantages", advantages, f32, (T, N)),
                                ("returns", returns, f32, (T, N))):
         if t is not None:
-            _check(name, t, dev, dt, shape)
+            check_tensor("gae_device", name, t, dev, dt, shape)
     L = load()
-    ptr = (lambda t: None if t is None else ctypes.c_void_p(t.data_ptr()))
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    index = torch.cuda.current_device() if dev.index is None else dev.index
-    rc = L.mrp_gae_device(index, ctypes.c_void_p(stream), T, N, ptr(rewards), ptr(values), ptr(episode_starts),
+    rc = L.mrp_gae_device(index_of(dev), stream_of(dev), T, N, ptr(rewards), ptr(values), ptr(episode_starts),
                           ptr(truncated), ptr(terminal_values), ptr(last_values), ptr(dones), float(gamma), float(gae_lambda),
                           ptr(advantages), ptr(returns))
     if rc == -1:
@@ -125,10 +111,10 @@ def collect_rollouts(env, policy, buffer, obs, episode_start, norm=None, eps_out
     N, T, dev = buffer.n_lanes, buffer.n_steps, buffer.device
     O, A = policy.obs_dim, policy.act_dim
     f32, u8 = torch.float32, torch.uint8
-    _check("obs", obs, dev, f32, (N, O))
-    _check("episode_start", episode_start, dev, u8, (N,))
+    check_tensor("collect_rollouts", "obs", obs, dev, f32, (N, O))
+    check_tensor("collect_rollouts", "episode_start", episode_start, dev, u8, (N,))
     if eps_out is not None:
-        _check("eps_out", eps_out, dev, f32, (T, N, A))
+        check_tensor("collect_rollouts", "eps_out", eps_out, dev, f32, (T, N, A))
     if tuple(buffer.obs_shape) != (O,) or buffer.act_dim != A:
         raise ValueError(f"collect_rollouts: the buffer holds obs {buffer.obs_shape} / {buffer.act_dim} actions, "
                          f"the policy takes ({O},) / {A}")

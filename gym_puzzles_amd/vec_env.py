@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._device import Handle, check_tensor, ptr, stream_of
 from ._native import ENV_IDS, STATUS_FAULT, STATUS_NONFINITE, Batch, env_dims
 from .spawn import ENV_CFG, V2_AGENT_IDS, V3_AGENT_IDS
 from .pixels import stack_shape
@@ -202,17 +203,22 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
     def step_torch(self, actions, obs, reward, done, truncated=None, terminal_obs=None, reward64=None, status=None):
         """One step on torch CUDA tensors on this env's device (float32 [N, A] actions, [N, O] obs,
         [N] reward, uint8 [N] done/truncated/status, optional [N, O] terminal_obs and float64 [N]
-        reward64), asynchronous on that device's current torch stream."""
+        reward64), asynchronous on that device's current torch stream.  ``actions`` may be None (the
+        device RNG's synthetic actions); a tensor of another dtype, shape or device, or one that is not
+        contiguous, raises ``ValueError`` before anything is launched."""
         import torch
         dev = torch.device("cuda", self.device)
-        for name, t in (("actions", actions), ("obs", obs), ("reward", reward), ("done", done), ("truncated", truncated),
-                        ("terminal_obs", terminal_obs), ("reward64", reward64), ("status", status)):
-            if t is not None and t.device != dev:
-                raise ValueError(f"step_torch: {name} is on {t.device}, this VecEnv runs on {dev}")
-        self._b.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = (lambda t: 0 if t is None else t.data_ptr())
-        self._b.step_device(ptr(actions), obs.data_ptr(), reward.data_ptr(), done.data_ptr(), ptr(truncated), ptr(status),
-                            ptr(terminal_obs), ptr(reward64))
+        N, O, A = self.num_envs, self._b.obs_dim, self._b.act_dim
+        f32, u8 = torch.float32, torch.uint8
+        for name, t, dt, shape, optional in (
+                ("actions", actions, f32, (N, A), True), ("obs", obs, f32, (N, O), False), ("reward", reward, f32, (N,), False),
+                ("done", done, u8, (N,), False), ("truncated", truncated, u8, (N,), True), ("status", status, u8, (N,), True),
+                ("terminal_obs", terminal_obs, f32, (N, O), True), ("reward64", reward64, torch.float64, (N,), True)):
+            if t is not None or not optional:
+                check_tensor("step_torch", name, t, dev, dt, shape)
+        self._b.set_stream(stream_of(dev))
+        self._b.step_device(ptr(actions), ptr(obs), ptr(reward), ptr(done), ptr(truncated), ptr(status), ptr(terminal_obs),
+                            ptr(reward64))
 
     def pixels_torch(self, done=None, out=None):
         """The zero-copy companion of ``step_torch`` for ``obs_type="image"``: renders every lane's
@@ -227,13 +233,9 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
         import torch
         dev = torch.device("cuda", self.device)
         shape = (self.num_envs,) + tuple(self.observation_space.shape)
-        for name, t in (("done", done), ("out", out)):
-            if t is not None and (t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous()):
-                raise ValueError(f"pixels_torch: {name} must be a contiguous uint8 tensor on {dev}")
-        if done is not None and done.numel() != self.num_envs:
-            raise ValueError(f"pixels_torch: done holds {done.numel()} entries for {self.num_envs} envs")
-        if out is not None and tuple(out.shape) != shape:
-            raise ValueError(f"pixels_torch: out is {tuple(out.shape)}, the stacks are {shape}")
+        for name, t, want in (("done", done, (self.num_envs,)), ("out", out, shape)):
+            if t is not None:
+                check_tensor("pixels_torch", name, t, dev, torch.uint8, want)
         if out is None:
             if self._pair is None:
                 self._pair = [torch.zeros(shape, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -250,34 +252,32 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
         return self._b
 
 
-class DeviceVecNormalize:
+class DeviceVecNormalize(Handle):
     """stable-baselines3 ``VecNormalize`` + ``Monitor`` statistics kept on the GPU (libmrp's
     ``mrp_norm_*``).  The reference wraps every env in ``Monitor`` and the vector
     env in ``VecNormalize`` with default arguments (``train/train.py:68,80-82``).  All arrays are
-    torch CUDA tensors on ``device``; calls are asynchronous on the current torch stream."""
+    contiguous torch CUDA tensors on ``device``, float32 unless stated; ``reset`` and ``step`` raise
+    ``ValueError`` for any other tensor before anything is launched.  The kernels are element-wise, so
+    an output may be its input (``obs_out is obs``).  Calls are asynchronous on the current torch stream."""
+
+    _DESTROY, _LAST_ERROR = "mrp_norm_destroy", "mrp_norm_last_error"
 
     def __init__(self, n_lanes: int, obs_dim: int, device: int = 0, clip_obs: float = 10.0, clip_reward: float = 10.0,
                  gamma: float = 0.99, epsilon: float = 1e-8):
-        import ctypes
-
-        from ._native import MrpError, load
-        self._L, self._err = load(), MrpError
+        import torch
         self.n_lanes, self.obs_dim, self.device = n_lanes, obs_dim, device
-        h = ctypes.c_void_p()
-        rc = self._L.mrp_norm_create(n_lanes, obs_dim, device, clip_obs, clip_reward, gamma, epsilon, ctypes.byref(h))
-        if rc != 0:
-            raise MrpError(f"mrp_norm_create failed ({rc}): {self._L.mrp_norm_last_error(None).decode()}")
-        self._h = h
+        self._dev = torch.device("cuda", device)
+        self._open("mrp_norm_create", n_lanes, obs_dim, device, clip_obs, clip_reward, gamma, epsilon)
         self._training = True
         self._norm_obs = True
 
-    def _check(self, rc):
-        if rc != 0:
-            raise self._err(self._L.mrp_norm_last_error(self._h).decode())
-
-    def _sync_stream(self):
-        import torch
-        self._check(self._L.mrp_norm_set_stream(self._h, torch.cuda.current_stream(self.device).cuda_stream))
+    def _launch(self, who, tensors, call, *args):
+        """Check every given tensor of ``tensors`` (name, tensor, dtype, shape, optional), then launch."""
+        for name, t, dtype, shape, optional in tensors:
+            if t is not None or not optional:
+                check_tensor(who, name, t, self._dev, dtype, shape)
+        self._check_rc(self._L.mrp_norm_set_stream(self._h, stream_of(self._dev)))
+        self._check_rc(call(self._h, *args))
 
     @property
     def training(self) -> bool:
@@ -286,7 +286,7 @@ class DeviceVecNormalize:
     @training.setter
     def training(self, value: bool):
         self._training = bool(value)
-        self._check(self._L.mrp_norm_set_training(self._h, int(self._training)))
+        self._check_rc(self._L.mrp_norm_set_training(self._h, int(self._training)))
 
     @property
     def norm_obs(self) -> bool:
@@ -296,24 +296,34 @@ class DeviceVecNormalize:
     def norm_obs(self, value: bool):
         """SB3 VecNormalize.norm_obs: the observation statistics only move while it is set."""
         self._norm_obs = bool(value)
-        self._check(self._L.mrp_norm_set_norm_obs(self._h, int(self._norm_obs)))
+        self._check_rc(self._L.mrp_norm_set_norm_obs(self._h, int(self._norm_obs)))
 
     def reset(self, obs, obs_out):
-        self._sync_stream()
-        self._check(self._L.mrp_norm_reset_device(self._h, obs.data_ptr(), obs_out.data_ptr()))
+        """``obs`` and ``obs_out``: float32 [N, O]."""
+        import torch
+        shape = (self.n_lanes, self.obs_dim)
+        tensors = (("obs", obs, torch.float32, shape, False), ("obs_out", obs_out, torch.float32, shape, False))
+        self._launch("DeviceVecNormalize.reset", tensors, self._L.mrp_norm_reset_device, ptr(obs), ptr(obs_out))
 
     def step(self, obs, reward, done, obs_out, reward_out, term_obs=None, term_out=None, ep_return=None, ep_len=None,
              reward64=None):
-        """``reward64`` (float64 [N], optional): the env's float64 rewards, which Monitor's
+        """float32 [N, O] ``obs`` / ``obs_out`` / ``term_obs`` / ``term_out``, float32 [N] ``reward`` /
+        ``reward_out``, uint8 [N] ``done``, float64 [N] ``ep_return`` and int32 [N] ``ep_len``.
+        ``reward64`` (float64 [N], optional): the env's float64 rewards, which Monitor's
         episode return then sums (SB3's Monitor sums the env's Python-float rewards)."""
-        ptr = (lambda t: None if t is None else t.data_ptr())
-        self._sync_stream()
-        self._check(self._L.mrp_norm_step_device_ex(self._h, ptr(obs), ptr(reward), ptr(reward64), ptr(done), ptr(term_obs),
-                                                     ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len)))
+        import torch
+        N, NO, f32, f64 = (self.n_lanes,), (self.n_lanes, self.obs_dim), torch.float32, torch.float64
+        tensors = (("obs", obs, f32, NO, False), ("reward", reward, f32, N, False), ("done", done, torch.uint8, N, False),
+                   ("obs_out", obs_out, f32, NO, False), ("reward_out", reward_out, f32, N, False),
+                   ("term_obs", term_obs, f32, NO, True), ("term_out", term_out, f32, NO, True),
+                   ("ep_return", ep_return, f64, N, True), ("ep_len", ep_len, torch.int32, N, True),
+                   ("reward64", reward64, f64, N, True))
+        self._launch("DeviceVecNormalize.step", tensors, self._L.mrp_norm_step_device_ex, ptr(obs), ptr(reward), ptr(reward64),
+                     ptr(done), ptr(term_obs), ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
 
     def get_stats(self) -> dict:
         st = np.zeros(2 * self.obs_dim + 4, np.float64)
-        self._check(self._L.mrp_norm_get_stats(self._h, st.ctypes.data))
+        self._check_rc(self._L.mrp_norm_get_stats(self._h, st.ctypes.data))
         D = self.obs_dim
         return {"obs_mean": st[:D], "obs_var": st[D:2 * D], "obs_count": st[2 * D], "ret_mean": st[2 * D + 1],
                 "ret_var": st[2 * D + 2], "ret_count": st[2 * D + 3]}
@@ -321,18 +331,7 @@ class DeviceVecNormalize:
     def set_stats(self, stats: dict) -> None:
         st = np.concatenate([np.asarray(stats["obs_mean"], np.float64), np.asarray(stats["obs_var"], np.float64),
                              [stats["obs_count"], stats["ret_mean"], stats["ret_var"], stats["ret_count"]]])
-        self._check(self._L.mrp_norm_set_stats(self._h, np.ascontiguousarray(st).ctypes.data))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mrp_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check_rc(self._L.mrp_norm_set_stats(self._h, np.ascontiguousarray(st).ctypes.data))
 
 
 class MultiRobotPuzzleVecNormalize:

@@ -278,7 +278,8 @@ int mrp_norm_set_stats(mrp_norm* n, const double* in);
  * n_lanes lanes x n_steps rows in one launch on `hip_stream` (NULL = the null stream) of `device`.
  * All arrays are device pointers, row-major [n_steps][n_lanes] except d_last_values / d_last_dones
  * [n_lanes].  d_truncated and d_terminal_values are both NULL (no bootstrap) or both given.
- * Outputs may not alias any input or each other.  Asynchronous.
+ * An output may overlap no input and not the other output (byte extents, so a view into an input's
+ * allocation that starts where the input ends is fine).  Asynchronous.
  * The rule, which the kernel matches bit for bit, is gym_puzzles_amd.rollout.gae_ref: truncated
  * elements first get reward += float32(gamma) * terminal_value (float32); then, from the last row
  * down, with nnt = 1 - (d_last_dones on the last row, the next row's episode_starts otherwise) and
@@ -288,7 +289,7 @@ int mrp_norm_set_stats(mrp_norm* n, const double* in);
  * with g32 = (float)gamma, c32 = (float)(gamma * gae_lambda), every operation rounded separately;
  * advantages = (float)L, returns = advantages + values (float32).
  * MRP_E_ARG: n_steps < 1, n_lanes < 1, a null required pointer, one bootstrap array without the
- * other, an output equal to an input or to the other output, a device index out of range.
+ * other, an output that overlaps an input or the other output, a device index out of range.
  * MRP_E_HIP: no device, launch failure.  The message is read with mrp_norm_last_error(NULL). */
 int mrp_gae_device(int device, void* hip_stream, int n_steps, int n_lanes,
                    const float* d_rewards, const float* d_values, const uint8_t* d_episode_starts,
@@ -316,18 +317,19 @@ int mrp_policy_create(int device, int obs_dim, int act_dim, int n_shared, int n_
                       int activation, mrp_policy** out);
 void mrp_policy_destroy(mrp_policy* p);
 const char* mrp_policy_last_error(const mrp_policy* p);
-/* Host pointers in torch's [out][in] layout: weights / biases hold n_shared + n_pi + n_vf + 2
- * entries (trunk, policy tower, value tower, action head, value head); std[i] is
+/* The length of the flat parameter vector: SB3's parameters() order, log_std, then trunk, policy
+ * tower, value tower, action head, value head, each weight row-major [out][in], then bias. */
+int mrp_policy_n_params(const mrp_policy* p);
+/* Host pointers: flat[mrp_policy_n_params] in that order and std[act_dim], std[i] being
  * float32(exp(float64(log_std[i]))), computed by the caller.  Packs the weights for the kernel and
  * copies them; synchronises the device. */
-int mrp_policy_set_params(mrp_policy* p, const float* const* weights, const float* const* biases, const float* log_std,
-                          const float* std);
+int mrp_policy_set_params(mrp_policy* p, const float* flat, const float* std);
 /* One launch on `hip_stream` (NULL = the null stream): d_obs [n_lanes][obs_dim]; noise d_eps_in
  * [n_lanes][act_dim], or NULL for the device counter RNG keyed by (seed, lane_offset + lane,
  * counter * act_dim + i) (Box-Muller in float64 rounded to float32); deterministic: action = mean.
  * Outputs: d_actions [n_lanes][act_dim] (unclipped, what SB3 stores), optional d_clipped (what
  * steps the env), d_values [n_lanes], d_log_probs [n_lanes] and d_eps_out (the noise used).
- * MRP_E_ARG: n_lanes < 1, a null d_obs / d_actions, an output equal to an input or to another
+ * MRP_E_ARG: n_lanes < 1, a null d_obs / d_actions, an output that overlaps an input or another
  * output; MRP_E_STATE before mrp_policy_set_params.  Asynchronous. */
 int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, const float* d_eps_in,
                           uint64_t seed, uint64_t lane_offset, uint64_t counter, int deterministic, float* d_actions,
@@ -337,29 +339,27 @@ int mrp_policy_act_device(mrp_policy* p, void* hip_stream, int n_lanes, const fl
 int mrp_policy_values_device(mrp_policy* p, void* hip_stream, int n_lanes, const float* d_obs, float* d_values);
 /* Device self-test of the policy's tanh rule (mrp_math.h tanh_f32) on n host inputs (host output). */
 int mrp_selftest_tanh(int device, const float* x, float* out, int n);
-/* The device's parameters in mrp_policy_set_params's layout, plus std: its inverse, e.g. after
+/* The device's parameters as mrp_policy_set_params takes them: its inverse, e.g. after
  * mrp_ppo_step_device.  Synchronises the device.  MRP_E_ARG: a null pointer; MRP_E_STATE before
  * mrp_policy_set_params. */
-int mrp_policy_get_params(mrp_policy* p, float* const* weights, float* const* biases, float* log_std, float* std);
+int mrp_policy_get_params(mrp_policy* p, float* flat, float* std);
 
 /* ---------------------------------------------------------------------------------------------
  * Device PPO update: one optimiser step of SB3's PPO.train() on a minibatch (evaluate_actions, the
  * clipped surrogate / value / entropy losses, the backward pass, global grad-norm clipping, Adam),
  * written into the policy's device parameters in place, with no host synchronisation and no
  * atomics.  The rule, which the kernels match bit for bit, is gym_puzzles_amd.ppo.ppo_grad_ref /
- * adam_ref (DESIGN.md "Device PPO update").  The flat parameter order is SB3's parameters():
- * log_std, then trunk, policy tower, value tower, action head, value head, each weight row-major
- * [out][in], then bias.
+ * adam_ref (DESIGN.md "Device PPO update").  The flat parameter order is mrp_policy_n_params's.
  * --------------------------------------------------------------------------------------------- */
 typedef struct mrp_ppo mrp_ppo;
-/* The optimiser of one policy (which must outlive it; one mrp_ppo per policy): master parameters,
+/* The optimiser of one policy (which must outlive it: every call reads it; one mrp_ppo per policy): master parameters,
  * gradient, Adam moments (zero) and a workspace for minibatches of up to max_batch samples.
  * MRP_E_ARG: a null pointer, max_batch outside 1..1048576 (message: mrp_ppo_last_error(NULL)).  A
  * later mrp_policy_set_params is picked up by the next call; the moments stay. */
 int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out);
 void mrp_ppo_destroy(mrp_ppo* o);
 const char* mrp_ppo_last_error(const mrp_ppo* o);
-/* The length of the flat parameter vector. */
+/* The length of the flat parameter vector: its policy's mrp_policy_n_params. */
 int mrp_ppo_n_params(const mrp_ppo* o);
 /* Gradients and statistics only: d_grad [n_params] takes the flat gradient before clipping, d_stats
  * [5] the policy loss, value loss, entropy loss, approx_kl and clip fraction.  Inputs: float32 device

@@ -330,3 +330,36 @@ def test_step_torch_rejects_tensors_on_another_device(gpu_lib):
     torch.cuda.synchronize(dev)
     assert torch.isfinite(obs).all()
     venv.close()
+
+
+@pytest.mark.gpu
+def test_step_torch_refuses_wrong_tensors_before_any_launch(gpu_lib):
+    """A tensor of the wrong dtype, length, layout or device would be an out-of-bounds device access:
+    each raises ValueError, and the lane state afterwards is bitwise what it was, so nothing ran."""
+    import torch
+
+    from gym_puzzles_amd import MultiRobotPuzzleVecEnv
+    n = 4
+    venv = MultiRobotPuzzleVecEnv(0, n, seed=1)
+    venv.reset()
+    dev = torch.device("cuda", 0)
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
+    act, obs, rew, done = z(n, 6), z(n, 28), z(n), z(n, dt=torch.uint8)
+    before = venv.batch.get_state()
+    wrong = {
+        "float64 obs": lambda: venv.step_torch(act, z(n, 28, dt=torch.float64), rew, done),
+        "short reward": lambda: venv.step_torch(act, obs, z(n - 1), done),
+        "bool done": lambda: venv.step_torch(act, obs, rew, z(n, dt=torch.bool)),
+        "non-contiguous obs": lambda: venv.step_torch(act, z(n, 56)[:, ::2], rew, done),
+        "CPU actions": lambda: venv.step_torch(act.cpu(), obs, rew, done),
+        "float32 reward64": lambda: venv.step_torch(act, obs, rew, done, reward64=z(n)),
+        "obs is no tensor": lambda: venv.step_torch(act, None, rew, done),
+    }
+    for what, call in wrong.items():
+        with pytest.raises(ValueError):
+            call()
+        assert np.array_equal(venv.batch.get_state(), before), what
+    venv.step_torch(act, obs, rew, done, truncated=z(n, dt=torch.uint8), terminal_obs=z(n, 28), reward64=z(n, dt=torch.float64),
+                    status=z(n, dt=torch.uint8))
+    assert not np.array_equal(venv.batch.get_state(), before) and torch.isfinite(obs).all()
+    venv.close()

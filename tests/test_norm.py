@@ -247,3 +247,45 @@ def test_device_norm_obs_off_matches_restatement(gpu_lib):
                                [ref.ret_rms.mean, ref.ret_rms.var, ref.ret_rms.count], rtol=1e-10)
     norm.close()
     b.close()
+
+
+@pytest.mark.gpu
+def test_device_vecnormalize_refuses_wrong_tensors_before_any_launch(gpu_lib):
+    """reset and step check every tensor (a float64 or short one would be an out-of-bounds device
+    access): each wrong one raises ValueError and the statistics afterwards are bitwise what they were."""
+    import torch
+
+    from gym_puzzles_amd import Batch, DeviceVecNormalize
+    n = 4
+    dev = torch.device("cuda", 0)
+    b = Batch(0, n, seed=2)
+    O = b.obs_dim
+    norm = DeviceVecNormalize(n, O, 0)
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
+    obs = torch.from_numpy(b.reset().copy()).to(dev)
+    nobs, rew, nrew, done = z(n, O), torch.ones(n, device=dev), z(n), z(n, dt=torch.uint8)
+    norm.reset(obs, nobs)
+    norm.step(obs, rew, done, nobs, nrew)
+    before = norm.get_stats()
+    wrong = {
+        "reset: float64 obs": lambda: norm.reset(obs.double(), nobs),
+        "reset: short obs": lambda: norm.reset(obs[:n - 1].contiguous(), nobs),
+        "reset: non-contiguous obs_out": lambda: norm.reset(obs, z(n, 2 * O)[:, ::2]),
+        "reset: CPU obs": lambda: norm.reset(obs.cpu(), nobs),
+        "step: float64 obs": lambda: norm.step(obs.double(), rew, done, nobs, nrew),
+        "step: short reward": lambda: norm.step(obs, rew[:n - 1].contiguous(), done, nobs, nrew),
+        "step: bool done": lambda: norm.step(obs, rew, done.bool(), nobs, nrew),
+        "step: non-contiguous obs_out": lambda: norm.step(obs, rew, done, z(n, 2 * O)[:, ::2], nrew),
+        "step: CPU reward_out": lambda: norm.step(obs, rew, done, nobs, nrew.cpu()),
+        "step: float32 ep_return": lambda: norm.step(obs, rew, done, nobs, nrew, ep_return=z(n)),
+        "step: int64 ep_len": lambda: norm.step(obs, rew, done, nobs, nrew, ep_len=z(n, dt=torch.int64)),
+    }
+    for what, call in wrong.items():
+        with pytest.raises(ValueError):
+            call()
+        after = norm.get_stats()
+        assert all(np.array_equal(np.asarray(after[k]), np.asarray(before[k])) for k in before), what
+    norm.step(obs, rew, done, obs, nrew)                      # element-wise: in place stays legal
+    assert norm.get_stats()["ret_count"] > before["ret_count"]
+    norm.close()
+    b.close()

@@ -270,6 +270,29 @@ def test_argument_errors(gpu_lib):
     pol.close()
 
 
+def test_outputs_may_touch_an_input_but_not_overlap_it(gpu_lib):
+    """The alias rule works on byte extents: an ``actions`` view into the allocation that holds ``obs`` is
+    refused when it covers the last 6 floats of ``obs`` and accepted when it starts exactly where ``obs``
+    ends (an extent one element too long would refuse that)."""
+    import torch
+    params, obs, eps, _ = _case("sb3-default")
+    N, O, A = 8, params.obs_dim, params.act_dim
+    d_eps = torch.from_numpy(eps[:N]).cuda()
+    big = torch.zeros(N * O + N * A, dtype=torch.float32, device="cuda")
+    d_obs = big[:N * O].view(N, O)
+    d_obs.copy_(torch.from_numpy(obs[:N]))
+    pol = P.DevicePolicy.from_params(params)
+    want = pol.act(d_obs.clone(), eps=d_eps)
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device="cuda")  # noqa: E731
+    with pytest.raises(ValueError, match="alias"):
+        pol.act(d_obs, eps=d_eps, out=(big[N * O - 6:N * O - 6 + N * A].view(N, A), z(N, A), z(N), z(N)))
+    _same(d_obs, obs[:N], "a refused call wrote nothing")
+    got = pol.act(d_obs, eps=d_eps, out=(big[N * O:].view(N, A), z(N, A), z(N), z(N)))
+    for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
+        _same(g, w.cpu().numpy(), f"actions behind obs: {what}")
+    pol.close()
+
+
 @pytest.mark.parametrize("with_norm", [False, True])
 def test_collect_rollouts_end_to_end(gpu_lib, with_norm):
     """collect_rollouts on MultiRobotPuzzle-v0, 64 lanes, 12 steps, a 5-step TimeLimit, the default

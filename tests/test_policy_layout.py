@@ -1,0 +1,108 @@
+"""The device policy's parameter map (csrc/mrp_policy_layout.h), checked on the host.
+
+mrp_policy_set_params scatters the flat parameter vector through this map into the device image,
+mrp_policy_get_params gathers it back and mrp_ppo_create takes its index tables from it, so it is the
+one place where a padding or stride mistake can be made.  tests/policy_layout_check.cpp walks the map
+for each architecture of tests/test_ppo_gpu.py (the two width-one ones and one-by-one are the smallest
+at which such a mistake shows); it is a stand-alone program built host-only with the address and
+undefined-behaviour sanitizers.  Here the map is compared with a numpy restatement of the image layout
+and with the flat order of gym_puzzles_amd.policy.flatten_params.
+"""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+from test_packed import _hipcc
+from test_ppo import make_params
+from test_ppo_gpu import ARCHS
+
+from gym_puzzles_amd import policy as P
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    hipcc = _hipcc()
+    if hipcc is None:
+        pytest.skip("hipcc not available")
+    out = tmp_path_factory.mktemp("policy_layout") / "policy_layout_check"
+    # the sanitizers instrument the host code only (-Xarch_host): no device code is built, let alone sanitized
+    subprocess.run([hipcc, "-std=c++17", "-O1", "-g", "-x", "hip", "--cuda-host-only", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-Xarch_host", "-fno-sanitize-recover=all", os.path.join(HERE, "policy_layout_check.cpp"), "-o", str(out)],
+                   check=True, capture_output=True)
+    return str(out)
+
+
+def _up(n, m):
+    return (n + m - 1) // m * m
+
+
+def image_ref(arch):
+    """The device image restated: ``({(slot, j, k): float offset}, n_floats)``, k = -1 for a bias and
+    slot = -1 for log_std.  Per hidden layer the weights ``[K][pad32(N)]`` and the bias ``[pad32(N)]``,
+    then the heads' rows padded to a multiple of 4, then log_std, then std; every block rounded up to 4
+    floats."""
+    obs_dim, act_dim, (S, Pn, V), widths, _ = arch
+    kt = widths[S - 1] if S else obs_dim
+    ins = [obs_dim if i == 0 and S else kt if i in (S, S + Pn) else widths[i - 1] for i in range(len(widths))]
+    where, off = {}, 0
+
+    def take(count):
+        nonlocal off
+        at, off = off, off + _up(count, 4)
+        return at
+    for slot, (K, N) in enumerate(zip(ins, widths)):
+        Np = _up(N, 32)
+        w, b = take(K * Np), take(Np)
+        for j in range(N):
+            where[slot, j, -1] = b + j
+            for k in range(K):
+                where[slot, j, k] = w + k * Np + j
+    kp = widths[S + Pn - 1] if Pn else kt
+    kv = widths[S + Pn + V - 1] if V else kt
+    for slot, outs, K in ((len(widths), act_dim, kp), (len(widths) + 1, 1, kv)):
+        w, b = take(outs * _up(K, 4)), take(outs)
+        for j in range(outs):
+            where[slot, j, -1] = b + j
+            for k in range(K):
+                where[slot, j, k] = w + j * _up(K, 4) + k
+    log_std = take(act_dim)
+    take(act_dim)                                            # std: in the image, not a parameter
+    for i in range(act_dim):
+        where[-1, i, -1] = log_std + i
+    return where, off
+
+
+@pytest.mark.parametrize("name", list(ARCHS))
+def test_parameter_map(exe, name):
+    arch = ARCHS[name]
+    obs_dim, act_dim, (S, Pn, V), widths, _ = arch
+    r = subprocess.run([exe, *map(str, (obs_dim, act_dim, S, Pn, V, *widths))], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = np.array(r.stdout.split(), np.int64)
+    n_floats, n_params = rows[:2]
+    got = rows[2:].reshape(-1, 5)                            # image, slot, j, k, rowmajor per flat index
+    where, want_floats = image_ref(arch)
+    assert n_floats == want_floats
+    assert n_params == len(got) == len(where)
+    image = got[:, 0]
+    assert [where[s, j, k] for _, s, j, k, _ in got.tolist()] == image.tolist(), "the map equals the restated layout"
+    assert len(set(image.tolist())) == n_params, "injective"
+    assert image.min() >= 0 and image.max() < n_floats - act_dim, "inside the image, below std"
+    # the flat order is flatten_params': every element of these parameters holds its own flat index
+    like = make_params(arch)
+    own = P.unflatten_params(like, np.arange(n_params, dtype=np.float32))
+    assert n_params < 2 ** 24 and np.array_equal(P.flatten_params(own), np.arange(n_params))
+    layers = P._layers(own)
+    for flat, (_, slot, j, k, rm) in enumerate(got.tolist()):
+        if slot < 0:
+            held = own.log_std[rm]
+        else:
+            w, b = layers[slot]
+            held = b[rm] if k < 0 else w.ravel()[rm]
+            assert 0 <= j < w.shape[0] and k < w.shape[1] and rm == (j if k < 0 else j * w.shape[1] + k)
+        assert held == flat, (flat, slot, j, k)

@@ -293,6 +293,29 @@ def test_inputs_are_not_written_and_argument_errors(gpu_lib):
         x.close()
 
 
+def test_calls_after_the_policy_is_closed_are_refused(gpu_lib):
+    """mrp_ppo keeps its policy's pointer and reads it in every call: after ``pol.close()`` that is freed
+    memory, so DevicePPO checks the policy's handle first."""
+    params, batch = _case("sb3-default")
+    B = 40
+    d = _dev(tuple(a[:B] for a in batch))
+    pol, ppo = _ppo(params, B)
+    ppo.step(*d)
+    pol.close()
+    with pytest.raises(ValueError, match="closed"):
+        ppo.step(*d)
+    with pytest.raises(ValueError, match="closed"):
+        ppo.grad(*d)
+    with pytest.raises(ValueError, match="closed"):
+        ppo.state()
+    with pytest.raises(ValueError, match="DevicePolicy is closed"):
+        pol.act(d[0])
+    ppo.close()
+    ppo.close()
+    with pytest.raises(ValueError, match="DevicePPO is closed|DevicePolicy is closed"):
+        ppo.step(*d)
+
+
 def ppo_fresh_grad(params, d, B):
     pol, ppo = _ppo(params, B)
     g, s = ppo.grad(*d)

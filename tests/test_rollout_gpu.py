@@ -191,3 +191,28 @@ def test_gae_device_argument_errors(gpu_lib):
         gae_device(d["r"], d["v"], d["es"], d["lv"], d["dones"], 0.99, 0.95, truncated=d["trunc"])
     with pytest.raises(ValueError):
         gae_device(d["r"], d["v"], d["es"], d["lv"], d["dones"], 0.99, 0.95, returns=d["v"])
+
+
+def test_gae_device_alias_rule_uses_byte_extents(gpu_lib):
+    """An output that overlaps an input by one element is refused, although it starts elsewhere; an
+    output that starts at the byte where a uint8 input ends is accepted (extents counted in elements
+    would see the 24 flags as 96 bytes and refuse it)."""
+    import torch
+    T, N = 4, 6
+    x = _inputs(T, N, seed=3)
+    d = _dev(x)
+    floats = torch.zeros(2 * T * N - 1, device="cuda")
+    values, returns = floats[:T * N].view(T, N), floats[T * N - 1:].view(T, N)     # returns starts on values' last element
+    values.copy_(d["v"])
+    with pytest.raises(ValueError, match="alias"):
+        _run(dict(d, v=values), 0.99, 0.95, True, returns=returns)
+    _same(values, x["v"], "a refused call wrote nothing")
+    raw = torch.zeros(T * N + 4 * T * N, dtype=torch.uint8, device="cuda")
+    starts, adv = raw[:T * N].view(T, N), raw[T * N:].view(torch.float32).view(T, N)  # advantages from byte 24 on
+    starts.copy_(d["es"])
+    want_a, want_r = _ref(x, 0.99, 0.95, True)
+    got_a, got_r = _run(dict(d, es=starts), 0.99, 0.95, True, advantages=adv)
+    assert got_a is adv
+    _same(got_a, want_a, "advantages behind episode_starts")
+    _same(got_r, want_r, "returns")
+    assert np.array_equal(starts.cpu().numpy(), x["es"]), "episode_starts was written"
