@@ -15,11 +15,13 @@ gym_puzzles env interface.  See DESIGN.md.
                            rollout.collect_rollouts runs act / step / normalise / add without a host sync
     DevicePPO              one optimiser step of SB3's PPO.train() on the device -- evaluate_actions, losses,
                            backward, grad-norm clip, Adam -- writing the DevicePolicy's parameters in place
-                           (ppo.ppo_grad_ref / adam_ref / ppo_train_ref / exp_ref state the rule in numpy)
+                           (ppo.ppo_grad_ref / adam_ref / ppo_train_ref / exp_ref state the rule in numpy), with
+                           SB3's clip_range_vf and target_kl (ppo.kl_stop_ref) and, with minibatch="device", the
+                           minibatch gather and advantage normalisation (ppo.normalize_adv_ref) in HIP
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
 from .policy import policy_ref, tanh_ref  # noqa: F401  (pure numpy)
-from .ppo import adam_ref, exp_ref, ppo_grad_ref, ppo_train_ref  # noqa: F401  (pure numpy)
+from .ppo import adam_ref, exp_ref, kl_stop_ref, normalize_adv_ref, ppo_grad_ref, ppo_train_ref  # noqa: F401  (pure numpy)
 
 
 def __getattr__(name):

@@ -106,6 +106,11 @@ ABI = {
     "mrp_ppo_grad_device": (_i, [_P, _P, _i] + [_P] * 5 + [_f, _f, _d, _P, _P]),
     "mrp_ppo_step_device": (_i, [_P, _P, _i] + [_P] * 5 + [_f, _f, _d, _d] + [_f] * 7 + [_P]),
     "mrp_ppo_get_state": (_i, [_P, _P, _P]),
+    "mrp_ppo_begin_device": (_i, [_P, _P]),
+    "mrp_ppo_minibatch_device": (_i, [_P, _P, _i, _P, ctypes.c_longlong] + [_P] * 6 + [_i, _f, _f, _d, _f, _d, _d] + [_f] * 7
+                                 + [_P, _P]),
+    "mrp_ppo_progress": (_i, [_P, _P, _ip, _ip]),
+    "mrp_ppo_get_staged": (_i, [_P, _i] + [_P] * 6),
     "mrp_selftest_exp": (_i, [_i, _P, _P, _i]),
 }
 EXPORTED = tuple(ABI)

@@ -21,6 +21,21 @@
 //                 factor, and the five statistics.
 //   k_ppo_adam    flat elementwise clip + Adam on the master vectors; writes both device images of the
 //                 parameters (k_policy's [K][Npad] one and the row-major one) and std = exp_f32(log_std).
+//
+// mrp_ppo_minibatch_device puts up to three launches in front of these (ppo.py normalize_adv_ref):
+//
+//   k_ppo_gather   copies the minibatch's indexed rows of the rollout fields into the optimiser's staging
+//                  buffers (a workgroup per 32 rows of a chunk, row reads coalesced); an index outside
+//                  [0, n_rows) reads row 0 and sets the sticky bad_index word; with normalize_advantage the
+//                  first workgroup of a chunk also writes the chunk's sequential float64 advantage sum.
+//   k_ppo_advnorm  two launches of a workgroup per chunk: <0> the chunk's float64 sum of squared deviations
+//                  from the mean, <1> the staged advantages normalised in place.  The chunk partials are
+//                  added in ascending order by one thread of every workgroup.
+//
+// and runs the step under a predicate: the object's device words {stopped, applied, bad_index}.  Every
+// kernel of such a call first loads `stopped` (wave-uniform, before any barrier) and returns when it is
+// set; k_ppo_norm sets it when kl_stop_ref holds, k_ppo_adam advances `applied`.  mrp_ppo_grad_device and
+// mrp_ppo_step_device pass a null predicate.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -45,6 +60,9 @@ constexpr int NL = 3 * P_MAXL;             // hidden layers at most (trunk, poli
 constexpr int L_ACT = NL, L_VAL = NL + 1;  // the heads' slots in the delta table
 constexpr int HW = 32;                     // row stride of the heads' delta / log_std-term arrays
 constexpr int NSTAT = 5, SW = 8;           // statistics, and the row stride of their per-sample terms
+constexpr int S_KL = 3;                    // approx_kl's place among the statistics
+constexpr int W_STOPPED = 0, W_APPLIED = 1, W_BAD_INDEX = 2, NWORDS = 4;   // the object's device progress words
+constexpr int G_ROWS = 32;                 // rows of a chunk whose observation and action rows one workgroup gathers
 
 struct PpoNet {
     Net net;
@@ -110,7 +128,9 @@ __device__ __forceinline__ int bwd_tower(const PpoNet& pn, const Layer* L, int l
 __global__ __launch_bounds__(P_NT) void k_ppo_fb(const PpoNet pn, int B, const float* __restrict__ obs,
                                                  const float* __restrict__ actions, const float* __restrict__ old_lp,
                                                  const float* __restrict__ adv_in, const float* __restrict__ ret_in, float clip,
-                                                 float vf2, float invB) {
+                                                 float vf2, float invB, const float* __restrict__ old_v, float cv,
+                                                 const int* pred) {
+    if (pred && *pred) return;
     __shared__ float lds[3 * P_TILE * P_LDA];
     __shared__ float hs[P_TILE * P_HS];     // the heads' outputs, then the log-prob terms, then the heads' deltas
     __shared__ float gs[P_TILE];
@@ -170,11 +190,20 @@ __global__ __launch_bounds__(P_NT) void k_ppo_fb(const PpoNet pn, int B, const f
             const float pl1 = adv * ratio, pl2 = adv * mrp::fmin_(mrp::fmax_(ratio, lo), hi);
             const bool first = pl1 <= pl2;
             g = first ? (-(adv * ratio)) * invB : 0.0f;
-            dv = ((v - ret) * vf2) * invB;
+            // clip_range_vf (old_v non-null): the value prediction is clamped to old_v +- cv, and the gradient
+            // passes where the clamp does (torch's clamp backward: inclusive at both ends)
+            float vp = v;
+            bool pass = true;
+            if (old_v) {
+                const float ov = old_v[n], dvo = v - ov;
+                vp = ov + mrp::fmin_(mrp::fmax_(dvo, -cv), cv);
+                pass = dvo >= -cv && dvo <= cv;
+            }
+            dv = pass ? ((vp - ret) * vf2) * invB : 0.0f;
             const float r1 = ratio - 1.0f;
             float* st = pn.sterm + (size_t)n * SW;
             st[0] = -(first ? pl1 : pl2);
-            st[1] = (ret - v) * (ret - v);
+            st[1] = (ret - vp) * (ret - vp);
             st[2] = -ent;
             st[3] = r1 - diff;
             st[4] = __builtin_fabsf(r1) > clip ? 1.0f : 0.0f;
@@ -242,7 +271,8 @@ __global__ __launch_bounds__(P_NT) void k_ppo_fb(const PpoNet pn, int B, const f
 // fma(delta[n][j], x[n][k], acc) from +0
 __global__ __launch_bounds__(P_NT) void k_ppo_wgrad(const WTile* __restrict__ tiles, int n_tiles, int B,
                                                     const float* __restrict__ obs, int obs_dim, float* __restrict__ partial,
-                                                    int n_params) {
+                                                    int n_params, const int* pred) {
+    if (pred && *pred) return;
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 31, h = l >> 5;
     const int n_chunks = (B + CHUNK - 1) / CHUNK;
     const int gid = blockIdx.x * (P_NT / 64) + wave;
@@ -300,7 +330,8 @@ __global__ __launch_bounds__(P_NT) void k_ppo_wgrad(const WTile* __restrict__ ti
 // sums the chunk's statistics terms in float64
 __global__ __launch_bounds__(P_NT) void k_ppo_bsum(const BElem* __restrict__ elems, int n_elems, int B,
                                                    const float* __restrict__ sterm, float* __restrict__ partial, int n_params,
-                                                   double* __restrict__ spart) {
+                                                   double* __restrict__ spart, const int* pred) {
+    if (pred && *pred) return;
     const int chunk = blockIdx.x, n0 = chunk * CHUNK, n1 = (B < n0 + CHUNK ? B : n0 + CHUNK);
     if (blockIdx.y == gridDim.y - 1) {
         if (threadIdx.x < NSTAT) {
@@ -319,7 +350,8 @@ __global__ __launch_bounds__(P_NT) void k_ppo_bsum(const BElem* __restrict__ ele
 }
 
 __global__ __launch_bounds__(P_NT) void k_ppo_reduce(const float* __restrict__ partial, int n_params, int n_chunks, int act_dim,
-                                                     float ent_coef, float* __restrict__ grad) {
+                                                     float ent_coef, float* __restrict__ grad, const int* pred) {
+    if (pred && *pred) return;
     const int e = blockIdx.x * P_NT + threadIdx.x;
     if (e >= n_params) return;
     float g = partial[e];
@@ -330,7 +362,9 @@ __global__ __launch_bounds__(P_NT) void k_ppo_reduce(const float* __restrict__ p
 
 __global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ grad, int n_params, double max_norm,
                                                    const double* __restrict__ spart, int n_chunks, int B,
-                                                   float* __restrict__ coef, float* __restrict__ stats) {
+                                                   float* __restrict__ coef, float* __restrict__ stats, int* words,
+                                                   double kl_limit) {
+    if (words && words[W_STOPPED]) return;
     __shared__ double part[P_NT];
     const int t = threadIdx.x;
     double acc = 0.0;
@@ -348,7 +382,10 @@ __global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ gra
     } else if (t <= NSTAT) {
         double sum = 0.0;
         for (int c = 0; c < n_chunks; ++c) sum = sum + spart[c * NSTAT + (t - 1)];
-        stats[t - 1] = (float)(sum * (1.0 / (double)B));
+        const float sv = (float)(sum * (1.0 / (double)B));
+        stats[t - 1] = sv;
+        // kl_stop_ref: this minibatch is not applied and nothing after it runs (kl_limit = 1.5 * target_kl, < 0: none)
+        if (t - 1 == S_KL && words && kl_limit >= 0.0 && (double)sv > kl_limit) words[W_STOPPED] = 1;
     }
 }
 
@@ -360,8 +397,10 @@ __global__ __launch_bounds__(P_NT) void k_ppo_adam(int n_params, int act_dim, co
                                                    const float* __restrict__ coef, float* __restrict__ param,
                                                    float* __restrict__ m, float* __restrict__ v, const int* __restrict__ fwd,
                                                    const int* __restrict__ row, float* __restrict__ image,
-                                                   float* __restrict__ rows, float* __restrict__ std, AdamK k) {
+                                                   float* __restrict__ rows, float* __restrict__ std, AdamK k, int* words) {
+    if (words && words[W_STOPPED]) return;
     const int e = blockIdx.x * P_NT + threadIdx.x;
+    if (e == 0 && words) words[W_APPLIED] = words[W_APPLIED] + 1;
     if (e >= n_params) return;
     const float g = grad[e] * coef[0];
     const float mn = (k.b1 * m[e]) + (k.omb1 * g);
@@ -385,6 +424,89 @@ __global__ __launch_bounds__(P_NT) void k_ppo_import(int n_params, const float* 
     if (row[e] >= 0) rows[row[e]] = p;
 }
 
+// the six rollout fields of a minibatch call: what the caller holds, and the optimiser's staging buffers
+struct Fields { const float *obs, *act, *old_v, *old_lp, *adv, *ret; };
+struct Stage { float *obs, *act, *old_v, *old_lp, *adv, *ret; };
+
+// grid (chunks, row groups of a chunk): staged row n = field row idx[n] (n itself without an index); row
+// group 0 also sums the chunk's advantages in sample order in float64 (sum_adv)
+__global__ __launch_bounds__(P_NT) void k_ppo_gather(const int* pred, int* words, int B, const long long* __restrict__ idx,
+                                                     long long n_rows, Fields f, Stage s, int D, int A, int sum_adv,
+                                                     double* __restrict__ advpart) {
+    if (*pred) return;
+    __shared__ long long rows[G_ROWS];
+    __shared__ float adv_s[CHUNK];
+    const int tid = threadIdx.x, n0 = blockIdx.x * CHUNK, r0 = n0 + blockIdx.y * G_ROWS;
+    if (r0 >= B) return;
+    auto row_of = [&](int n) {
+        long long r = idx ? idx[n] : (long long)n;
+        if (r < 0 || r >= n_rows) { r = 0; words[W_BAD_INDEX] = 1; }
+        return r;
+    };
+    const int cnt = B - r0 < G_ROWS ? B - r0 : G_ROWS;
+    if (tid < cnt) {
+        const long long r = row_of(r0 + tid);
+        rows[tid] = r;
+        const int n = r0 + tid;
+        s.old_lp[n] = f.old_lp[r]; s.adv[n] = f.adv[r]; s.ret[n] = f.ret[r];
+        if (f.old_v) s.old_v[n] = f.old_v[r];
+    }
+    __syncthreads();
+    for (int e = tid; e < cnt * D; e += P_NT) {
+        const int row = e / D, k = e - row * D;
+        s.obs[(size_t)(r0 + row) * D + k] = f.obs[(size_t)rows[row] * D + k];
+    }
+    for (int e = tid; e < cnt * A; e += P_NT) {
+        const int row = e / A, k = e - row * A;
+        s.act[(size_t)(r0 + row) * A + k] = f.act[(size_t)rows[row] * A + k];
+    }
+    if (sum_adv && blockIdx.y == 0) {
+        const int c = B - n0 < CHUNK ? B - n0 : CHUNK;
+        if (tid < c) adv_s[tid] = f.adv[row_of(n0 + tid)];
+        __syncthreads();
+        if (tid == 0) {
+            double acc = 0.0;
+            for (int i = 0; i < c; ++i) acc = acc + (double)adv_s[i];
+            advpart[blockIdx.x] = acc;
+        }
+    }
+}
+
+// normalize_adv_ref on the staged advantages, a workgroup per chunk.  sum[] and sq[] hold the chunks' float64
+// partials; PHASE 0 writes sq[chunk] = the sequential sum of (adv - mean)^2, PHASE 1 writes adv in place.
+template <int PHASE>
+__global__ __launch_bounds__(P_NT) void k_ppo_advnorm(const int* pred, int B, int n_chunks, float* __restrict__ adv,
+                                                      const double* __restrict__ sum, double* sq) {
+    if (*pred) return;
+    __shared__ double sh[CHUNK];
+    __shared__ double bc[2];
+    const int tid = threadIdx.x, n0 = blockIdx.x * CHUNK, n = n0 + tid;
+    if (tid == 0) {
+        double acc = 0.0;
+        for (int c = 0; c < n_chunks; ++c) acc = acc + sum[c];
+        bc[0] = acc * (1.0 / (double)B);
+        if (PHASE == 1) {
+            double q = 0.0;
+            for (int c = 0; c < n_chunks; ++c) q = q + sq[c];
+            bc[1] = sqrt(q / (double)(B - 1)) + 1e-8;
+        }
+    }
+    __syncthreads();
+    const double dev = n < B ? (double)adv[n] - bc[0] : 0.0;
+    if (PHASE == 0) {
+        sh[tid] = dev * dev;
+        __syncthreads();
+        if (tid == 0) {
+            const int c = B - n0 < CHUNK ? B - n0 : CHUNK;
+            double acc = 0.0;
+            for (int i = 0; i < c; ++i) acc = acc + sh[i];
+            sq[blockIdx.x] = acc;
+        }
+    } else if (n < B) {
+        adv[n] = (float)(dev / bc[1]);
+    }
+}
+
 __global__ void k_exp(const float* __restrict__ x, float* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = mrp::exp_f32(x[i]);
@@ -406,20 +528,30 @@ struct mrp_ppo {
     int* d_idx = nullptr;         // fwd[n_params], row[n_params]
     WTile* d_tiles = nullptr;
     BElem* d_elems = nullptr;
+    float* d_stage = nullptr;     // the staged minibatch: obs, actions, old_values, old_log_probs, advantages, returns
+    double* d_advpart = nullptr;  // [2][max_chunks]: the chunks' advantage sums, then their sums of squared deviations
+    int* d_words = nullptr;       // stopped, applied, bad_index
     std::string err;
     float* param() const { return d_vec; }
     float* grad() const { return d_vec + n_params; }
     float* m() const { return d_vec + 2 * (size_t)n_params; }
     float* v() const { return d_vec + 3 * (size_t)n_params; }
     float* coef() const { return d_vec + 4 * (size_t)n_params; }
+    Stage stage() const {
+        const size_t mb = (size_t)max_batch;
+        float* q = d_stage + mb * (pn.net.obs_dim + pn.net.act_dim);
+        return Stage{d_stage, d_stage + mb * pn.net.obs_dim, q, q + mb, q + 2 * mb, q + 3 * mb};
+    }
 };
 
 namespace {
 
-// gradients and statistics of one minibatch into `d_grad` (the object's own vector when null) and d_stats
+// gradients and statistics of one minibatch into `d_grad` (the object's own vector when null) and d_stats.
+// old_v: clip_range_vf's old values (cv), null for none.  words: the progress words of a predicated call
+// (null: none); kl_limit >= 0 lets k_ppo_norm set `stopped`.
 int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const float* obs, const float* actions, const float* old_lp,
                     const float* adv, const float* ret, float clip, float ent_coef, double vf_coef, double max_norm, float* d_grad,
-                    float* d_stats) {
+                    float* d_stats, const float* old_v = nullptr, float cv = -1.0f, int* words = nullptr, double kl_limit = -1.0) {
     auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
     if (B < 1) return bad("B < 1");
     if (B > o->max_batch) return bad("B > max_batch");
@@ -439,15 +571,26 @@ int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const fl
     }
     const int n_chunks = (B + CHUNK - 1) / CHUNK;
     hipLaunchKernelGGL(k_ppo_fb, dim3((B + P_TILE - 1) / P_TILE), dim3(P_NT), 0, st, o->pn, B, obs, actions, old_lp, adv, ret, clip,
-                       (float)(2.0 * vf_coef), (float)(1.0 / (double)B));
+                       (float)(2.0 * vf_coef), (float)(1.0 / (double)B), old_v, cv, words);
     const int waves = o->n_tiles * n_chunks;
     hipLaunchKernelGGL(k_ppo_wgrad, dim3((waves + 3) / 4), dim3(P_NT), 0, st, o->d_tiles, o->n_tiles, B, obs, o->pn.net.obs_dim,
-                       o->d_partial, P);
+                       o->d_partial, P, words);
     hipLaunchKernelGGL(k_ppo_bsum, dim3(n_chunks, (o->n_elems + P_NT - 1) / P_NT + 1), dim3(P_NT), 0, st, o->d_elems, o->n_elems, B,
-                       o->pn.sterm, o->d_partial, P, o->d_spart);
+                       o->pn.sterm, o->d_partial, P, o->d_spart, words);
     float* g = d_grad ? d_grad : o->grad();
-    hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g);
-    hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats);
+    hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g, words);
+    hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats, words,
+                       kl_limit);
+    MRP_HIPCHK(o, hipGetLastError());
+    return MRP_OK;
+}
+
+// clip + Adam on the object's own gradient; `words` as in ppo_grad_launch
+int ppo_adam_launch(mrp_ppo* o, hipStream_t st, AdamK k, int* words) {
+    const int P = o->n_params;
+    mrp_policy* p = o->policy;
+    hipLaunchKernelGGL(k_ppo_adam, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, st, P, p->net.act_dim, o->grad(), o->coef(), o->param(),
+                       o->m(), o->v(), o->d_idx, o->d_idx + P, p->d_params, o->d_rows, const_cast<float*>(p->net.std), k, words);
     MRP_HIPCHK(o, hipGetLastError());
     return MRP_OK;
 }
@@ -464,7 +607,8 @@ void mrp_ppo_destroy(mrp_ppo* o) {
     if (!o) return;
     (void)hipSetDevice(o->device);
     (void)hipDeviceSynchronize();
-    void* ptrs[] = {o->d_ws, o->d_rows, o->d_vec, o->d_partial, o->d_spart, o->d_idx, o->d_tiles, o->d_elems};
+    void* ptrs[] = {o->d_ws, o->d_rows, o->d_vec, o->d_partial, o->d_spart, o->d_idx, o->d_tiles, o->d_elems,
+                    o->d_stage, o->d_advpart, o->d_words};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     delete o;
@@ -533,6 +677,9 @@ int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out) {
     alloc((void**)&o->d_partial, (size_t)o->max_chunks * P * sizeof(float));
     alloc((void**)&o->d_spart, (size_t)o->max_chunks * NSTAT * sizeof(double));
     alloc((void**)&o->d_idx, 2 * (size_t)P * sizeof(int));
+    alloc((void**)&o->d_stage, (size_t)max_batch * (D + A + 4) * sizeof(float));
+    alloc((void**)&o->d_advpart, 2 * (size_t)o->max_chunks * sizeof(double));
+    alloc((void**)&o->d_words, NWORDS * sizeof(int));
     if (e == hipSuccess) {
         for (int li = 0; li < nl; ++li) {
             const Layer& L = *layers[li];
@@ -593,13 +740,92 @@ int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs,
     const int rc = ppo_grad_launch(o, "mrp_ppo_step_device", (hipStream_t)hip_stream, B, d_obs, d_actions, d_old_log_probs,
                                    d_advantages, d_returns, clip_range, ent_coef, vf_coef, max_grad_norm, nullptr, d_stats);
     if (rc != MRP_OK) return rc;
-    const int P = o->n_params;
-    mrp_policy* p = o->policy;
-    const AdamK k{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps};
-    hipLaunchKernelGGL(k_ppo_adam, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, (hipStream_t)hip_stream, P, p->net.act_dim, o->grad(),
-                       o->coef(), o->param(), o->m(), o->v(), o->d_idx, o->d_idx + P, p->d_params, o->d_rows,
-                       const_cast<float*>(p->net.std), k);
-    MRP_HIPCHK(o, hipGetLastError());
+    return ppo_adam_launch(o, (hipStream_t)hip_stream, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps},
+                           nullptr);
+}
+
+int mrp_ppo_begin_device(mrp_ppo* o, void* hip_stream) {
+    if (!o) return MRP_E_ARG;
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipMemsetAsync(o->d_words, 0, NWORDS * sizeof(int), (hipStream_t)hip_stream));
+    return MRP_OK;
+}
+
+int mrp_ppo_minibatch_device(mrp_ppo* o, void* hip_stream, int B, const long long* d_index, long long n_rows, const float* d_obs,
+                             const float* d_actions, const float* d_old_values, const float* d_old_log_probs,
+                             const float* d_advantages, const float* d_returns, int normalize_advantage, float clip_range,
+                             float clip_range_vf, double target_kl, float ent_coef, double vf_coef, double max_grad_norm,
+                             float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
+                             float step_size, float eps, float* d_grad, float* d_stats) {
+    if (!o) return MRP_E_ARG;
+    const char* who = "mrp_ppo_minibatch_device";
+    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
+    if (B < 1) return bad("B < 1");
+    if (B > o->max_batch) return bad("B > max_batch");
+    if (!d_obs || !d_actions || !d_old_log_probs || !d_advantages || !d_returns || !d_stats) return bad("null pointer");
+    if (!(clip_range_vf < 0.0f) && !d_old_values) return bad("clip_range_vf is set and d_old_values is null");
+    if (d_index && n_rows < 1) return bad("n_rows < 1");
+    if (clip_range_vf < 0.0f) d_old_values = nullptr;
+    const Net& net = o->pn.net;
+    const size_t f = sizeof(float), rows = d_index ? (size_t)n_rows : (size_t)B;
+    if (const char* what = check_outputs({{d_index, (size_t)B * sizeof(long long)}, {d_obs, rows * net.obs_dim * f},
+                                          {d_actions, rows * net.act_dim * f}, {d_old_values, rows * f}, {d_old_log_probs, rows * f},
+                                          {d_advantages, rows * f}, {d_returns, rows * f}},
+                                         {{d_stats, NSTAT * f}, {d_grad, (size_t)o->n_params * f}}))
+        return bad(what);
+    if (!o->policy->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    Fields in{d_obs, d_actions, d_old_values, d_old_log_probs, d_advantages, d_returns};
+    const bool norm = normalize_advantage && B > 1;      // SB3 skips a minibatch of one sample
+    if (d_index || norm) {
+        const Stage sg = o->stage();
+        const int n_chunks = (B + CHUNK - 1) / CHUNK, first = B < CHUNK ? B : CHUNK;
+        hipLaunchKernelGGL(k_ppo_gather, dim3(n_chunks, (first + G_ROWS - 1) / G_ROWS), dim3(P_NT), 0, st, o->d_words, o->d_words, B,
+                           d_index, (long long)rows, in, sg, net.obs_dim, net.act_dim, norm ? 1 : 0, o->d_advpart);
+        if (norm) {
+            double* sq = o->d_advpart + o->max_chunks;
+            hipLaunchKernelGGL(k_ppo_advnorm<0>, dim3(n_chunks), dim3(P_NT), 0, st, o->d_words, B, n_chunks, sg.adv, o->d_advpart, sq);
+            hipLaunchKernelGGL(k_ppo_advnorm<1>, dim3(n_chunks), dim3(P_NT), 0, st, o->d_words, B, n_chunks, sg.adv, o->d_advpart, sq);
+        }
+        in = Fields{sg.obs, sg.act, d_old_values ? sg.old_v : nullptr, sg.old_lp, sg.adv, sg.ret};
+    }
+    // the gradient alone (d_grad): no clip, no Adam, no stop
+    const int rc = ppo_grad_launch(o, who, st, B, in.obs, in.act, in.old_lp, in.adv, in.ret, clip_range, ent_coef, vf_coef,
+                                   d_grad ? 1.0 : max_grad_norm, d_grad, d_stats, in.old_v, clip_range_vf, o->d_words,
+                                   d_grad || target_kl < 0.0 ? -1.0 : 1.5 * target_kl);
+    if (rc != MRP_OK || d_grad) return rc;
+    return ppo_adam_launch(o, st, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps}, o->d_words);
+}
+
+int mrp_ppo_progress(mrp_ppo* o, void* hip_stream, int* stopped, int* applied) {
+    if (!o) return MRP_E_ARG;
+    if (!stopped || !applied) { o->err = "mrp_ppo_progress: null pointer"; return MRP_E_ARG; }
+    int w[NWORDS] = {};
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipStreamSynchronize((hipStream_t)hip_stream));
+    MRP_HIPCHK(o, hipMemcpy(w, o->d_words, sizeof(w), hipMemcpyDeviceToHost));
+    *stopped = w[W_STOPPED]; *applied = w[W_APPLIED];
+    if (w[W_BAD_INDEX]) {
+        o->err = "mrp_ppo_progress: an index outside [0, n_rows) since mrp_ppo_begin_device (row 0 was read in its place)";
+        return MRP_E_ARG;
+    }
+    return MRP_OK;
+}
+
+int mrp_ppo_get_staged(mrp_ppo* o, int B, float* obs, float* actions, float* old_values, float* old_log_probs, float* advantages,
+                       float* returns) {
+    if (!o) return MRP_E_ARG;
+    if (B < 1 || B > o->max_batch) { o->err = "mrp_ppo_get_staged: B outside 1..max_batch"; return MRP_E_ARG; }
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipDeviceSynchronize());
+    const Stage sg = o->stage();
+    const size_t nB = (size_t)B * sizeof(float);
+    const struct { float* dst; const float* src; size_t bytes; } copies[] = {
+        {obs, sg.obs, nB * o->pn.net.obs_dim}, {actions, sg.act, nB * o->pn.net.act_dim}, {old_values, sg.old_v, nB},
+        {old_log_probs, sg.old_lp, nB}, {advantages, sg.adv, nB}, {returns, sg.ret, nB}};
+    for (const auto& c : copies)
+        if (c.dst) MRP_HIPCHK(o, hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
     return MRP_OK;
 }
 

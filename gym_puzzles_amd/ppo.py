@@ -4,8 +4,8 @@
 write the device policy's parameters in place (``csrc/mrp_ppo.hip``, ``mrp_ppo_*`` in
 ``include/mrp.h``), with no host synchronisation and no atomics.
 
-``ppo_grad_ref``, ``adam_ref`` and ``ppo_train_ref`` are the numpy statement of the rule and the
-definition the kernels match bit for bit.  Everything is float32 with every operation rounded on its
+``ppo_grad_ref``, ``adam_ref``, ``normalize_adv_ref``, ``kl_stop_ref`` and ``ppo_train_ref`` are the numpy
+statement of the rule and the definition the kernels match bit for bit.  Everything is float32 with every operation rounded on its
 own unless stated otherwise; ``B`` is the minibatch size, ``invB = float32(1.0 / B)``.
 
 * ``exp_ref``: this build's float32 exp (``csrc/mrp_math.h`` ``exp_f32``), operation for operation;
@@ -14,7 +14,11 @@ own unless stated otherwise; ``B`` is the minibatch size, ``invB = float32(1.0 /
   action; the entropy is ``sum_i((0.5 + LOG_SQRT_2PI) + log_std_i)`` ascending from +0;
 * loss terms: ``ratio = exp(log_prob - old_log_prob)``, ``pl1 = adv * ratio``, ``pl2 = adv *
   fmin_(fmax_(ratio, 1 - c), 1 + c)``, the policy term ``-(pl1 <= pl2 ? pl1 : pl2)``, the value term
-  ``(ret - v) * (ret - v)``; ``clip_range_vf`` and ``target_kl`` are not built;
+  ``(ret - v) * (ret - v)``;
+* ``clip_range_vf`` (``cv``, with the rollout's ``old_values``): ``dv = v - old_v``, ``vp = old_v +
+  fmin_(fmax_(dv, -cv), cv)``, the value term ``(ret - vp) * (ret - vp)``, and ``dvalue = ((vp - ret) *
+  float32(2 * vf_coef)) * invB`` where ``dv >= -cv and dv <= cv`` (torch's clamp backward is inclusive at
+  both ends), ``+0`` elsewhere; without it ``vp`` is ``v`` and every sample passes;
 * upstream gradients: ``g = (pl1 <= pl2) ? (-(adv * ratio)) * invB : +0``, ``dmean_i = g * (d_i /
   (std_i * std_i))``, the ``log_std`` term ``g * ((d_i * d_i) / (std_i * std_i) - 1)``, ``dvalue =
   ((v - ret) * float32(2 * vf_coef)) * invB``;
@@ -34,11 +38,20 @@ own unless stated otherwise; ``B`` is the minibatch size, ``invB = float32(1.0 /
   ``weight`` row-major, then ``bias``: SB3's ``parameters()``); float64 sum of squares, partial ``t``
   (0..255) over elements ``t, t + 256, ...``, then the partials ascending; ``coef = float32(min(1,
   max_grad_norm / (sqrt(sum) + 1e-6)))``; every gradient is multiplied by ``coef``;
-* Adam (``adam_ref`` holds the operation order), then ``std = exp_ref(log_std)``.
+* Adam (``adam_ref`` holds the operation order), then ``std = exp_ref(log_std)``;
+* ``normalize_adv_ref``: SB3's ``(adv - adv.mean()) / (adv.std() + 1e-8)`` on a minibatch in float64, each
+  operation rounded alone: ``mean = chunk sum of adv * (1.0 / B)``, ``dev_i = float64(adv_i) - mean``, ``var
+  = chunk sum of dev * dev / (B - 1)``, ``out_i = float32(dev_i / (sqrt(var) + 1e-8))``; the chunk sums are
+  the statistics' (``CHUNK`` samples sequential from 0.0, then the chunks sequential); one sample is
+  returned as it is;
+* ``target_kl`` (``kl_stop_ref``): after a minibatch's statistics, ``float64(approx_kl) > 1.5 *
+  float64(target_kl)`` (strict) means that this minibatch is not applied and the whole ``train`` call
+  ends; ``ppo_train_ref`` holds the order.
 
-``normalize_advantage`` in ``DevicePPO`` is torch arithmetic on the gathered minibatch and lies
-outside the bitwise rule: the rule takes the advantages it is given.  The module is pure numpy at
-import; ``DevicePPO`` imports torch when used.
+``DevicePPO(minibatch="device")`` gathers the minibatch and normalises its advantages by this rule in HIP;
+with ``minibatch="torch"`` (the default) the gather is ``index_select`` and ``normalize_advantage`` is
+torch arithmetic on the gathered minibatch, outside the bitwise rule: the rule takes the advantages it
+is given.  The module is pure numpy at import; ``DevicePPO`` imports torch when used.
 """
 from __future__ import annotations
 
@@ -167,9 +180,13 @@ def evaluate_actions_ref(params, obs, actions):
     return v, lp, ent
 
 
-def ppo_grad_ref(params, obs, actions, old_log_probs, advantages, returns, clip_range=0.2, ent_coef=0.0, vf_coef=0.5):
+def ppo_grad_ref(params, obs, actions, old_log_probs, advantages, returns, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, *,
+                 old_values=None, clip_range_vf=None):
     """The flat gradient (float32, ``flatten_params`` order) of SB3's PPO loss on one minibatch and the
-    five statistics (float32 [5], ``STAT_NAMES``), by the rule of the module docstring."""
+    five statistics (float32 [5], ``STAT_NAMES``), by the rule of the module docstring.  ``clip_range_vf``
+    (with ``old_values`` [B], the rollout's value predictions) is SB3's value clipping."""
+    if clip_range_vf is not None and old_values is None:
+        raise ValueError("ppo_grad_ref: clip_range_vf needs old_values")
     obs = np.ascontiguousarray(obs, _f32)
     B, A = obs.shape[0], params.act_dim
     actions = np.ascontiguousarray(actions, _f32).reshape(B, A)
@@ -188,7 +205,15 @@ def ppo_grad_ref(params, obs, actions, old_log_probs, advantages, returns, clip_
         pl1, pl2 = adv * ratio, adv * clamped
         first = pl1 <= pl2
         p_term = -np.where(first, pl1, pl2)
-        v_term = (ret - v) * (ret - v)
+        if clip_range_vf is None:
+            vp, passed = v, np.ones(B, bool)
+        else:
+            old_v, cv = np.ascontiguousarray(old_values, _f32).reshape(B), _f32(clip_range_vf)
+            dv = v - old_v
+            cl = np.where(dv > -cv, dv, -cv)                         # fmax_(dv, -cv), then fmin_(., cv)
+            cl = np.where(cl < cv, cl, cv).astype(_f32)
+            vp, passed = old_v + cl, (dv >= -cv) & (dv <= cv)
+        v_term = (ret - vp) * (ret - vp)
         kl_term = (ratio - _f32(1.0)) - diff
         clip_term = (np.abs(ratio - _f32(1.0)) > c).astype(_f32)
         e_term = np.full(B, -ent, _f32)
@@ -197,7 +222,7 @@ def ppo_grad_ref(params, obs, actions, old_log_probs, advantages, returns, clip_
         g = np.where(first, (-(adv * ratio)) * invB, _f32(0.0)).astype(_f32)
         dmean = g[:, None] * (d / var)
         ls_term = g[:, None] * ((d * d) / var - _f32(1.0))
-        dvalue = (((v - ret) * vf2) * invB)[:, None]
+        dvalue = np.where(passed, ((vp - ret) * vf2) * invB, _f32(0.0)).astype(_f32)[:, None]
 
         grads = {}
 
@@ -268,27 +293,68 @@ def adam_ref(p, grad, state, lr, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5
     return (np.ascontiguousarray(p, _f32) - step * (state.m / denom)).astype(_f32), coef
 
 
+def normalize_adv_ref(adv):
+    """SB3's ``(adv - adv.mean()) / (adv.std() + 1e-8)`` (unbiased std) on one minibatch by the rule of
+    the module docstring: float64, every operation rounded alone, the sums in the statistics' chunk order,
+    one rounding to float32.  A single sample comes back unchanged, as SB3 skips it."""
+    adv = np.ascontiguousarray(adv, _f32).reshape(-1)
+    B = adv.size
+    if B == 1:
+        return adv.copy()
+    mean = _chunk_sum64(adv) * (1.0 / B)
+    dev = adv.astype(_f64) - mean
+    var = _chunk_sum64(dev * dev) / (B - 1)
+    return (dev / (math.sqrt(var) + 1e-8)).astype(_f32)
+
+
+def kl_stop_ref(approx_kl_stat, target_kl):
+    """SB3's early stop on the rule's float32 ``approx_kl`` statistic: strictly above ``1.5 * target_kl``."""
+    return bool(_f64(approx_kl_stat) > 1.5 * _f64(target_kl))
+
+
 def ppo_step_ref(params, state, batch, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
-                 betas=(0.9, 0.999), eps=1e-5):
+                 betas=(0.9, 0.999), eps=1e-5, *, old_values=None, clip_range_vf=None):
     """``ppo_grad_ref`` then ``adam_ref`` on one minibatch ``(obs, actions, old_log_probs, advantages,
     returns)``; returns ``(new params with std = exp_ref(log_std), stats)``."""
-    grad, stats = ppo_grad_ref(params, *batch, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef)
+    grad, stats = ppo_grad_ref(params, *batch, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, old_values=old_values,
+                               clip_range_vf=clip_range_vf)
+    return _apply_ref(params, state, grad, lr, max_grad_norm, betas, eps), stats
+
+
+def _apply_ref(params, state, grad, lr, max_grad_norm, betas, eps):
     flat, _ = adam_ref(flatten_params(params), grad, state, lr, max_grad_norm, betas, eps)
-    return unflatten_params(params, flat, std=exp_ref(flat[:params.act_dim])), stats
+    return unflatten_params(params, flat, std=exp_ref(flat[:params.act_dim]))
 
 
-def ppo_train_ref(params, state, data, epochs, batch_size, **hp):
+def ppo_train_ref(params, state, data, epochs, batch_size, *, old_values=None, normalize_advantage=False, clip_range_vf=None,
+                  target_kl=None, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, betas=(0.9, 0.999),
+                  eps=1e-5):
     """SB3's ``PPO.train()`` loop on host arrays: ``data = (obs, actions, old_log_probs, advantages,
-    returns)`` with the samples along axis 0, ``epochs`` one index array per epoch (the shuffled sample
-    order); every epoch is cut into consecutive minibatches of ``batch_size`` (the last may be short),
-    one ``ppo_step_ref`` each.  Returns ``(params, stats [n_updates, 5])``; ``state.t`` counts the steps."""
+    returns)`` (and ``old_values`` for ``clip_range_vf``) with the samples along axis 0, ``epochs`` one index
+    array per epoch (the shuffled sample order); every epoch is cut into consecutive minibatches of
+    ``batch_size`` (the last may be short).  A minibatch is evaluated (its advantages through
+    ``normalize_adv_ref`` first with ``normalize_advantage``) and its statistics row appended; with
+    ``target_kl``, if ``kl_stop_ref`` holds it is not applied and the whole call ends; otherwise the clip
+    and Adam are applied.  Returns ``(params, stats [n_evaluated, 5])``, the stopping minibatch's row
+    included; ``state.t`` counts the applied steps only."""
     stats = []
+    stop = False
     for order in epochs:
         order = np.asarray(order)
         for s in range(0, order.size, int(batch_size)):
             idx = order[s:s + int(batch_size)]
-            params, st = ppo_step_ref(params, state, tuple(np.asarray(a)[idx] for a in data), **hp)
+            obs, actions, old_lp, adv, ret = (np.asarray(a)[idx] for a in data)
+            if normalize_advantage:
+                adv = normalize_adv_ref(adv)
+            grad, st = ppo_grad_ref(params, obs, actions, old_lp, adv, ret, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                                    old_values=None if old_values is None else np.asarray(old_values)[idx], clip_range_vf=clip_range_vf)
             stats.append(st)
+            stop = target_kl is not None and kl_stop_ref(st[3], target_kl)
+            if stop:
+                break
+            params = _apply_ref(params, state, grad, lr, max_grad_norm, betas, eps)
+        if stop:
+            break
     return params, np.array(stats, _f32).reshape(-1, 5)
 
 
@@ -296,21 +362,37 @@ def ppo_train_ref(params, state, data, epochs, batch_size, **hp):
 class DevicePPO(Handle):
     """The rule on the device: ``grad`` is ``ppo_grad_ref``, ``step`` is ``ppo_step_ref`` written into
     ``policy``'s device parameters in place (the next ``policy.act`` uses them), ``train`` is SB3's
-    epoch / minibatch loop over a ``DeviceRolloutBuffer``.  Nothing here synchronises the device; the
-    statistics stay in device tensors.  The optimiser state (master parameters, gradient, Adam moments)
-    belongs to this object; ``policy.set_params`` afterwards is picked up by the next call and leaves
-    the moments as they are.  ``learning_rate`` is read at every step.  The library reads ``policy``'s
-    handle in every call, so a call after ``policy.close()`` raises ``ValueError``."""
+    epoch / minibatch loop over a ``DeviceRolloutBuffer`` (``ppo_train_ref``).  ``train``, ``step`` and
+    ``grad`` never synchronise the device; the statistics stay in device tensors.  The optimiser state
+    (master parameters, gradient, Adam moments) belongs to this object; ``policy.set_params`` afterwards is
+    picked up by the next call and leaves the moments as they are.  ``learning_rate`` is read at every
+    step.  The library reads ``policy``'s handle in every call, so a call after ``policy.close()`` raises
+    ``ValueError``.
+
+    ``clip_range_vf`` and ``target_kl`` are SB3's options (None: off).  ``target_kl`` acts in ``train``
+    and is decided on the device: after such a ``train`` the step count ``t``, ``n_applied`` and ``stopped``
+    are read back (one ``mrp_ppo_progress``, which synchronises) when first asked for, and the next ``step``
+    / ``train`` asks, because Adam's bias correction needs ``t``.  ``minibatch="device"`` gathers each
+    minibatch and normalises its advantages (``normalize_adv_ref``) in HIP; ``"torch"`` (the default) is
+    ``index_select`` and torch arithmetic."""
 
     _DESTROY, _LAST_ERROR, _VALUE_ERRORS = "mrp_ppo_destroy", "mrp_ppo_last_error", (-1, -3)
 
     def __init__(self, policy, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
-                 max_grad_norm=0.5, normalize_advantage=True, betas=(0.9, 0.999), eps=1e-5, max_batch=None):
+                 max_grad_norm=0.5, normalize_advantage=True, betas=(0.9, 0.999), eps=1e-5, max_batch=None, clip_range_vf=None,
+                 target_kl=None, minibatch="torch"):
+        if minibatch not in ("torch", "device"):
+            raise ValueError(f"DevicePPO: minibatch is {minibatch!r}, expected 'torch' or 'device'")
+        if clip_range_vf is not None and not clip_range_vf >= 0:
+            raise ValueError("DevicePPO: clip_range_vf must be None or >= 0")
+        if target_kl is not None and not target_kl >= 0:
+            raise ValueError("DevicePPO: target_kl must be None or >= 0")
         self.policy, self.learning_rate, self.n_epochs, self.batch_size = policy, learning_rate, int(n_epochs), int(batch_size)
         self.clip_range, self.ent_coef, self.vf_coef, self.max_grad_norm = clip_range, ent_coef, vf_coef, max_grad_norm
         self.normalize_advantage, self.betas, self.eps = bool(normalize_advantage), tuple(betas), eps
+        self.clip_range_vf, self.target_kl, self.minibatch = clip_range_vf, target_kl, minibatch
         self.max_batch = int(self.batch_size if max_batch is None else max_batch)
-        self.t = 0
+        self._t, self._n_applied, self._stopped, self._pending, self._staged = 0, 0, False, False, None
         self.device = policy.device
         self._open("mrp_ppo_create", policy._h, self.max_batch)
         self.n_params = int(self._L.mrp_ppo_n_params(self._h))
@@ -320,20 +402,70 @@ class DevicePPO(Handle):
         self.policy._h     # mrp_ppo reads the policy's handle in every call: ValueError once that is closed
         return super()._h
 
-    def _batch(self, obs, actions, old_log_probs, advantages, returns):
+    # ---- the step count and the device's progress words
+    def progress(self):
+        """``(stopped, applied)`` of the device's progress words since the last ``train`` / ``step`` /
+        ``grad`` began (``mrp_ppo_progress``: synchronises the stream).  ``ValueError`` if a gathered
+        index lay outside the fields' rows."""
+        stopped, applied = ctypes.c_int(), ctypes.c_int()
+        self._check_rc(self._L.mrp_ppo_progress(self._h, stream_of(self.device), ctypes.byref(stopped), ctypes.byref(applied)))
+        return bool(stopped.value), int(applied.value)
+
+    def _resolve(self):
+        if self._pending:
+            self._pending = False         # cleared first: a bad index raises once and leaves t at its base
+            self._stopped, self._n_applied = self.progress()
+            self._t += self._n_applied
+
+    @property
+    def t(self):
+        """Optimiser steps applied so far (Adam's step count)."""
+        self._resolve()
+        return self._t
+
+    @t.setter
+    def t(self, value):
+        self._resolve()
+        self._t = int(value)
+
+    @property
+    def n_applied(self):
+        """Steps the last ``train`` applied."""
+        self._resolve()
+        return self._n_applied
+
+    @property
+    def stopped(self):
+        """Whether the last ``train`` ended at ``target_kl``."""
+        self._resolve()
+        return self._stopped
+
+    # ---- one minibatch
+    def _batch(self, obs, actions, old_log_probs, advantages, returns, old_values=None, index=None):
         import torch
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
             raise ValueError("DevicePPO: obs must be a [B, obs_dim] CUDA tensor")
-        B, f32 = int(obs.shape[0]), torch.float32
-        if B < 1:
+        rows, f32 = int(obs.shape[0]), torch.float32
+        if index is None:
+            B = rows
+        else:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1:
+                raise ValueError("DevicePPO: index must be a 1-d int64 CUDA tensor")
+            B = int(index.shape[0])
+            check_tensor("DevicePPO", "index", index, self.device, torch.int64, (B,))
+        if B < 1 or rows < 1:
             raise ValueError("DevicePPO: the minibatch holds no sample")
-        named = (("obs", obs, (B, self.policy.obs_dim)), ("actions", actions, (B, self.policy.act_dim)),
-                 ("old_log_probs", old_log_probs, (B,)), ("advantages", advantages, (B,)), ("returns", returns, (B,)))
+        if self.clip_range_vf is not None and old_values is None:
+            raise ValueError("DevicePPO: clip_range_vf is set and old_values is missing")
+        named = (("obs", obs, (rows, self.policy.obs_dim)), ("actions", actions, (rows, self.policy.act_dim)),
+                 ("old_values", old_values, (rows,)), ("old_log_probs", old_log_probs, (rows,)), ("advantages", advantages, (rows,)),
+                 ("returns", returns, (rows,)))
         for name, t, shape in named:
-            check_tensor("DevicePPO", name, t, self.device, f32, shape)
+            if t is not None:
+                check_tensor("DevicePPO", name, t, self.device, f32, shape)
         if B > self.max_batch:
             raise ValueError(f"DevicePPO: a minibatch of {B} samples, max_batch is {self.max_batch}")
-        return B, [ptr(t) for _, t, _ in named]
+        return B, rows, [ptr(t) for _, t, _ in named]
 
     def _out(self, name, t, n):
         import torch
@@ -342,46 +474,137 @@ class DevicePPO(Handle):
         check_tensor("DevicePPO", name, t, self.device, torch.float32, (n,))
         return t
 
-    def grad(self, obs, actions, old_log_probs, advantages, returns, out=None, stats_out=None):
+    def _begin(self):
+        self._resolve()
+        self._check_rc(self._L.mrp_ppo_begin_device(self._h, stream_of(self.device)))
+
+    def _minibatch(self, stream, B, index, rows, ptrs, normalize, target_kl, t, grad, stats):
+        """One ``mrp_ppo_minibatch_device`` on checked pointers; ``t`` is the step this would be."""
+        f, d = ctypes.c_float, ctypes.c_double
+        sc = adam_scalars(t, self.learning_rate, self.betas, self.eps)
+        cv = -1.0 if self.clip_range_vf is None else self.clip_range_vf
+        self._check_rc(self._L.mrp_ppo_minibatch_device(
+            self._h, stream, B, index, rows, *ptrs, 1 if normalize else 0, f(self.clip_range), f(cv),
+            d(-1.0 if target_kl is None else target_kl), f(self.ent_coef), d(self.vf_coef), d(self.max_grad_norm),
+            *[f(float(x)) for x in sc], grad, stats))
+        if index is not None or (normalize and B > 1):
+            self._staged = B
+
+    def _extended(self, old_values, index, normalize):
+        return old_values is not None or index is not None or normalize or self.clip_range_vf is not None
+
+    def grad(self, obs, actions, old_log_probs, advantages, returns, out=None, stats_out=None, *, old_values=None, index=None,
+             normalize=False):
         """``ppo_grad_ref`` on the device: returns ``(flat_grad [n_params], stats [5])`` device
         tensors (``out`` / ``stats_out`` when given).  Parameters and optimiser state are not changed.
-        An output whose memory overlaps an input's or the other output's anywhere raises ``ValueError``."""
-        B, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns)
+        An output whose memory overlaps an input's or the other output's anywhere raises ``ValueError``.
+
+        ``old_values`` [B] is read under ``clip_range_vf``.  With ``index`` (int64 [B]) the fields hold any
+        number of rows and the minibatch is rows ``index`` of them, gathered on the device; ``normalize``
+        passes the advantages through ``normalize_adv_ref`` on the device first."""
+        B, rows, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns, old_values, index)
         g, st = self._out("out", out, self.n_params), self._out("stats_out", stats_out, 5)
+        if self._extended(old_values, index, normalize):
+            self._begin()
+            self._minibatch(stream_of(self.device), B, ptr(index), rows, ptrs, normalize, None, 1, ptr(g), ptr(st))
+            return g, st
         f = ctypes.c_float
+        del ptrs[2]
         self._check_rc(self._L.mrp_ppo_grad_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
                                                    ctypes.c_double(self.vf_coef), ptr(g), ptr(st)))
         return g, st
 
-    def step(self, obs, actions, old_log_probs, advantages, returns, stats_out=None):
-        """One optimiser step (``ppo_step_ref``) in place; returns the ``stats [5]`` device tensor."""
-        B, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns)
+    def step(self, obs, actions, old_log_probs, advantages, returns, stats_out=None, *, old_values=None, index=None,
+             normalize=False):
+        """One optimiser step (``ppo_step_ref``) in place; returns the ``stats [5]`` device tensor.
+        ``old_values``, ``index`` and ``normalize`` as in ``grad``.  ``target_kl`` belongs to ``train``:
+        a ``step`` is always applied."""
+        B, rows, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns, old_values, index)
         st = self._out("stats_out", stats_out, 5)
+        if self._extended(old_values, index, normalize):
+            self._begin()
+            self._minibatch(stream_of(self.device), B, ptr(index), rows, ptrs, normalize, None, self._t + 1, None, ptr(st))
+            self._t += 1
+            return st
         sc = adam_scalars(self.t + 1, self.learning_rate, self.betas, self.eps)
         f = ctypes.c_float
+        del ptrs[2]
         self._check_rc(self._L.mrp_ppo_step_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
                                                    ctypes.c_double(self.vf_coef), ctypes.c_double(self.max_grad_norm),
                                                    *[f(float(x)) for x in sc], ptr(st)))
-        self.t += 1
+        self._t += 1
         return st
 
-    def train(self, buffer, generator=None):
-        """``n_epochs`` passes over ``buffer.get(batch_size, generator)``, one ``step`` per minibatch;
-        returns the ``[n_updates, 5]`` device tensor of statistics.  ``normalize_advantage`` is SB3's
-        ``(adv - adv.mean()) / (adv.std() + 1e-8)`` as torch operations on the gathered minibatch
-        (unbiased std, skipped for one sample): outside the bitwise rule."""
+    def train(self, buffer, generator=None, poll=False):
+        """``n_epochs`` passes over the buffer's shuffled minibatches (``buffer.get``'s ``randperm`` and
+        flat order), one optimiser step each (``ppo_train_ref``); returns the ``[n_updates, 5]`` device
+        tensor of statistics and never synchronises.
+
+        With ``minibatch="torch"`` the minibatches are ``buffer.get``'s and ``normalize_advantage`` is
+        SB3's ``(adv - adv.mean()) / (adv.std() + 1e-8)`` as torch operations (unbiased std, skipped for
+        one sample): outside the bitwise rule.  With ``"device"`` gather and ``normalize_adv_ref`` run in
+        HIP, one library call per minibatch.  With ``target_kl`` every minibatch is still enqueued; those
+        from the stopping one on do nothing on the device and their statistics rows stay zero.
+        ``poll=True`` reads ``stopped`` after each epoch (a synchronisation) and stops enqueueing: the
+        results are the same."""
         import torch
         total = buffer.n_steps * buffer.n_lanes
         per_epoch = -(-total // self.batch_size)
         stats = torch.zeros(self.n_epochs * per_epoch, 5, dtype=torch.float32, device=self.device)
         u = 0
+        if self.minibatch == "torch" and self.clip_range_vf is None and self.target_kl is None:
+            for _ in range(self.n_epochs):
+                for obs, actions, _, old_lp, adv, ret in buffer.get(self.batch_size, generator):
+                    if self.normalize_advantage and adv.numel() > 1:
+                        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+                    self.step(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, stats_out=stats[u])
+                    u += 1
+            self._n_applied, self._stopped = u, False
+            return stats
+        self._begin()
+        t0, stream, kl = self._t, stream_of(self.device), self.target_kl
+        use_v = self.clip_range_vf is not None
+        if self.minibatch == "device":
+            obs, actions, values, old_lp, adv, ret = buffer.flat_fields()
+            _, rows, ptrs = self._batch(obs.reshape(total, -1), actions, old_lp, adv, ret, values if use_v else None,
+                                        index=torch.zeros(1, dtype=torch.int64, device=self.device))
         for _ in range(self.n_epochs):
-            for obs, actions, _, old_lp, adv, ret in buffer.get(self.batch_size, generator):
-                if self.normalize_advantage and adv.numel() > 1:
-                    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-                self.step(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, stats_out=stats[u])
-                u += 1
+            if self.minibatch == "device":
+                flat = buffer.flat_index(generator)
+                for start in range(0, total, self.batch_size):
+                    idx = flat[start:start + self.batch_size]
+                    if idx.shape[0] > self.max_batch:
+                        raise ValueError(f"DevicePPO: a minibatch of {idx.shape[0]} samples, max_batch is {self.max_batch}")
+                    self._minibatch(stream, int(idx.shape[0]), idx.data_ptr(), rows, ptrs, self.normalize_advantage, kl, t0 + u + 1,
+                                    None, stats[u].data_ptr())
+                    u += 1
+            else:
+                for obs, actions, values, old_lp, adv, ret in buffer.get(self.batch_size, generator):
+                    if self.normalize_advantage and adv.numel() > 1:
+                        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+                    B, rows, ptrs = self._batch(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, values if use_v else None)
+                    self._minibatch(stream, B, None, rows, ptrs, False, kl, t0 + u + 1, None, stats[u].data_ptr())
+                    u += 1
+            if poll and kl is not None and self.progress()[0]:
+                break
+        if kl is None:
+            self._t, self._n_applied, self._stopped = t0 + u, u, False
+        else:
+            self._pending = True
         return stats
+
+    def staged(self):
+        """Host copies of the staging buffers as the last gathered or device-normalised minibatch left
+        them: a dict of ``obs``, ``actions``, ``old_values`` (under ``clip_range_vf``), ``old_log_probs``,
+        ``advantages``, ``returns`` (synchronises the device).  For tests."""
+        if self._staged is None:
+            raise ValueError("DevicePPO.staged: no minibatch has been staged")
+        B = self._staged
+        out = {"obs": np.zeros((B, self.policy.obs_dim), _f32), "actions": np.zeros((B, self.policy.act_dim), _f32),
+               "old_values": np.zeros(B, _f32) if self.clip_range_vf is not None else None, "old_log_probs": np.zeros(B, _f32),
+               "advantages": np.zeros(B, _f32), "returns": np.zeros(B, _f32)}
+        self._check_rc(self._L.mrp_ppo_get_staged(self._h, B, *[None if a is None else a.ctypes.data for a in out.values()]))
+        return {k: a for k, a in out.items() if a is not None}
 
     def state(self):
         """``(m, v)``: host copies of Adam's moments, flat float32 (synchronises the device)."""

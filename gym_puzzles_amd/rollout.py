@@ -205,21 +205,31 @@ class DeviceRolloutBuffer:
         return gae_device(self.rewards, self.values, self.episode_starts, last_values, dones, self.gamma, self.gae_lambda,
                           self.truncated, self.terminal_values, self.advantages, self.returns)
 
+    def flat_index(self, generator=None):
+        """One epoch's sample order: a ``torch.randperm`` of the T*N samples in SB3's ``swap_and_flatten``
+        order (sample ``i`` is lane ``i // T``, row ``i % T``) as int64 row numbers into ``flat_fields``."""
+        import torch
+        if not self.full:
+            raise RuntimeError("DeviceRolloutBuffer: the buffer is not full")
+        T, N = self.n_steps, self.n_lanes
+        gdev = self.device if generator is None else generator.device
+        perm = torch.randperm(T * N, generator=generator, device=gdev).to(self.device)
+        return (perm % T) * N + perm // T     # row-major [T, N] position of sample i
+
+    def flat_fields(self):
+        """``[observations, actions, values, log_probs, advantages, returns]`` as row-major ``[T*N, ...]``
+        views of the buffer's tensors."""
+        total = self.n_steps * self.n_lanes
+        fields = (self.observations, self.actions, self.values, self.log_probs, self.advantages, self.returns)
+        return [f.reshape(total, *f.shape[2:]) for f in fields]
+
     def get(self, batch_size=None, generator=None):
         """Yield ``(observations, actions, old_values, old_log_prob, advantages, returns)`` minibatches
         that follow a ``torch.randperm`` of the T*N samples in SB3's ``swap_and_flatten`` order: flat
         index ``i`` is lane ``i // T``, row ``i % T``.  ``batch_size=None``: one batch of everything;
         the last batch holds the remainder."""
-        import torch
-        if not self.full:
-            raise RuntimeError("DeviceRolloutBuffer.get: the buffer is not full")
-        T, N = self.n_steps, self.n_lanes
-        total = T * N
-        gdev = self.device if generator is None else generator.device
-        perm = torch.randperm(total, generator=generator, device=gdev).to(self.device)
-        flat = (perm % T) * N + perm // T     # row-major [T, N] position of sample i
-        fields = (self.observations, self.actions, self.values, self.log_probs, self.advantages, self.returns)
-        fields = [f.reshape(total, *f.shape[2:]) for f in fields]
+        flat, fields = self.flat_index(generator), self.flat_fields()
+        total = self.n_steps * self.n_lanes
         batch_size = total if batch_size is None else int(batch_size)
         for start in range(0, total, batch_size):
             idx = flat[start:start + batch_size]

@@ -380,6 +380,40 @@ int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs,
                         float one_minus_beta2, float sqrt_bc2, float step_size, float eps, float* d_stats);
 /* Host copies of Adam's moments, n_params floats each.  Synchronises the device. */
 int mrp_ppo_get_state(mrp_ppo* o, float* m, float* v);
+/* ---- SB3's train() loop with target_kl, clip_range_vf and the minibatch gather on the device.  The
+ * object keeps three device words: `stopped` (a minibatch's approx_kl exceeded 1.5 * target_kl: that
+ * minibatch was not applied and nothing after it runs), `applied` (optimiser steps applied) and a sticky
+ * `bad_index`.  mrp_ppo_begin_device clears them (asynchronous); a train() call is one begin and one
+ * mrp_ppo_minibatch_device per minibatch, with no host synchronisation in between. */
+int mrp_ppo_begin_device(mrp_ppo* o, void* hip_stream);
+/* One minibatch of B samples under the predicate: every kernel first loads `stopped` and returns when it
+ * is set, so a skipped minibatch writes nothing, its d_stats row included.
+ *   fields   d_obs [rows][obs_dim], d_actions [rows][act_dim], d_old_values, d_old_log_probs, d_advantages,
+ *            d_returns [rows] (float32).  d_index (int64 [B]) names the minibatch's rows among rows = n_rows
+ *            (a rollout buffer's flat [T * N] view): they are gathered into the object's staging buffers.  An
+ *            index outside [0, n_rows) reads row 0 and sets bad_index (mrp_ppo_progress reports it).
+ *            d_index NULL: the fields are the B rows themselves (n_rows is ignored).
+ *   options  normalize_advantage != 0: the (staged) advantages are normalised by ppo.normalize_adv_ref
+ *            (skipped for B = 1); clip_range_vf < 0: none (d_old_values may be NULL and is not read), else
+ *            SB3's value clipping; target_kl < 0: none, else ppo.kl_stop_ref decides on the device.
+ *   d_grad   non-NULL: the gradient before clipping and the statistics only, as mrp_ppo_grad_device: no
+ *            clip, no Adam, no stop.  NULL: the step, with the Adam scalars of mrp_ppo_step_device.
+ * MRP_E_ARG as mrp_ppo_grad_device (the alias rule covers d_index and every field over all its rows), and:
+ * clip_range_vf >= 0 with d_old_values NULL, n_rows < 1.  No allocation, no synchronisation. */
+int mrp_ppo_minibatch_device(mrp_ppo* o, void* hip_stream, int B, const long long* d_index, long long n_rows,
+                             const float* d_obs, const float* d_actions, const float* d_old_values,
+                             const float* d_old_log_probs, const float* d_advantages, const float* d_returns,
+                             int normalize_advantage, float clip_range, float clip_range_vf, double target_kl, float ent_coef,
+                             double vf_coef, double max_grad_norm, float beta1, float one_minus_beta1, float beta2,
+                             float one_minus_beta2, float sqrt_bc2, float step_size, float eps, float* d_grad, float* d_stats);
+/* Synchronises the stream and returns the words.  MRP_E_ARG (with both words still returned) when
+ * bad_index is set. */
+int mrp_ppo_progress(mrp_ppo* o, void* hip_stream, int* stopped, int* applied);
+/* Host copies of the first B rows of the staging buffers as the last indexed or normalising
+ * mrp_ppo_minibatch_device left them (NULL outputs are skipped; old_values are staged only under
+ * clip_range_vf).  Synchronises the device.  For tests. */
+int mrp_ppo_get_staged(mrp_ppo* o, int B, float* obs, float* actions, float* old_values, float* old_log_probs,
+                       float* advantages, float* returns);
 /* Device self-test of the exp rule (mrp_math.h exp_f32) on n host inputs (host output). */
 int mrp_selftest_exp(int device, const float* x, float* out, int n);
 
