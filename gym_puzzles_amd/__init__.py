@@ -17,11 +17,14 @@ gym_puzzles env interface.  See DESIGN.md.
                            backward, grad-norm clip, Adam -- writing the DevicePolicy's parameters in place
                            (ppo.ppo_grad_ref / adam_ref / ppo_train_ref / exp_ref state the rule in numpy), with
                            SB3's clip_range_vf and target_kl (ppo.kl_stop_ref) and, with minibatch="device", the
-                           minibatch gather and advantage normalisation (ppo.normalize_adv_ref) in HIP
+                           minibatch gather and advantage normalisation (ppo.normalize_adv_ref) in HIP; with a
+                           dist.Shard / dist.GradExchange, data-parallel training: the ranks' gradients combined
+                           in rank order, clip and Adam on the device (ppo.combine_ref / ppo_train_dist_ref)
 """
 from ._native import ENV_IDS, Batch, MrpError, env_dims  # noqa: F401
 from .policy import policy_ref, tanh_ref  # noqa: F401  (pure numpy)
-from .ppo import adam_ref, exp_ref, kl_stop_ref, normalize_adv_ref, ppo_grad_ref, ppo_train_ref  # noqa: F401  (pure numpy)
+from .ppo import (adam_ref, combine_ref, exp_ref, kl_stop_ref, normalize_adv_ref, ppo_grad_ref,  # noqa: F401  (pure numpy)
+                  ppo_train_dist_ref, ppo_train_ref)
 
 
 def __getattr__(name):

@@ -111,6 +111,8 @@ ABI = {
                                  + [_P, _P]),
     "mrp_ppo_progress": (_i, [_P, _P, _ip, _ip]),
     "mrp_ppo_get_staged": (_i, [_P, _i] + [_P] * 6),
+    "mrp_ppo_apply_device": (_i, [_P, _P, _i, _P, ctypes.c_longlong, _d, _d] + [_f] * 7 + [_P]),
+    "mrp_ppo_set_state": (_i, [_P, _P, _P]),
     "mrp_selftest_exp": (_i, [_i, _P, _P, _i]),
 }
 EXPORTED = tuple(ABI)

@@ -36,6 +36,14 @@
 // kernel of such a call first loads `stopped` (wave-uniform, before any barrier) and returns when it is
 // set; k_ppo_norm sets it when kl_stop_ref holds, k_ppo_adam advances `applied`.  mrp_ppo_grad_device and
 // mrp_ppo_step_device pass a null predicate.
+//
+// mrp_ppo_apply_device is the data-parallel apply phase (ppo.py combine_ref): it starts from R ranks'
+// gradients and statistics instead of a minibatch, under the same predicate, in three launches:
+//
+//   k_ppo_combine  elementwise over the n_params + 5 floats of a rank's part: the R rows added in ascending
+//                  rank order (plain float32 adds), one multiply by float32(1 / R); writes the master
+//                  gradient, the caller's statistics row and the word k_ppo_norm<true> reads approx_kl from.
+//   k_ppo_norm<true>, k_ppo_adam   as above, on the combined values.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -360,6 +368,9 @@ __global__ __launch_bounds__(P_NT) void k_ppo_reduce(const float* __restrict__ p
     grad[e] = g;
 }
 
+// COMBINED (mrp_ppo_apply_device): the statistics are k_ppo_combine's, and kl_stop_ref reads the combined
+// approx_kl from coef[1]; spart, n_chunks, B and stats are not used
+template <bool COMBINED>
 __global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ grad, int n_params, double max_norm,
                                                    const double* __restrict__ spart, int n_chunks, int B,
                                                    float* __restrict__ coef, float* __restrict__ stats, int* words,
@@ -379,6 +390,8 @@ __global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ gra
         for (int i = 0; i < P_NT; ++i) sum = sum + part[i];
         const double q = max_norm / (sqrt(sum) + 1e-6);
         coef[0] = (float)(q < 1.0 ? q : 1.0);
+    } else if (COMBINED) {
+        if (t == 1 && words && kl_limit >= 0.0 && (double)coef[1] > kl_limit) words[W_STOPPED] = 1;
     } else if (t <= NSTAT) {
         double sum = 0.0;
         for (int c = 0; c < n_chunks; ++c) sum = sum + spart[c * NSTAT + (t - 1)];
@@ -386,6 +399,26 @@ __global__ __launch_bounds__(P_NT) void k_ppo_norm(const float* __restrict__ gra
         stats[t - 1] = sv;
         // kl_stop_ref: this minibatch is not applied and nothing after it runs (kl_limit = 1.5 * target_kl, < 0: none)
         if (t - 1 == S_KL && words && kl_limit >= 0.0 && (double)sv > kl_limit) words[W_STOPPED] = 1;
+    }
+}
+
+// combine_ref: element e of the R rows of `parts` (row stride `stride` floats) added in ascending row order,
+// then times inv_r = float32(1 / R).  Elements [0, n_params) are the gradient, [n_params, n_params + NSTAT) the
+// statistics: those go to `stats`, and approx_kl also to `kl` for k_ppo_norm<true>.
+__global__ __launch_bounds__(P_NT) void k_ppo_combine(const float* __restrict__ parts, int R, size_t stride, int n_params,
+                                                      float inv_r, float* __restrict__ grad, float* __restrict__ stats,
+                                                      float* __restrict__ kl, const int* words) {
+    if (words[W_STOPPED]) return;
+    const int e = blockIdx.x * P_NT + threadIdx.x;
+    if (e >= n_params + NSTAT) return;
+    float g = parts[e];
+    for (int r = 1; r < R; ++r) g = g + parts[(size_t)r * stride + e];
+    g = g * inv_r;
+    if (e < n_params) {
+        grad[e] = g;
+    } else {
+        stats[e - n_params] = g;
+        if (e - n_params == S_KL) kl[0] = g;
     }
 }
 
@@ -522,7 +555,7 @@ struct mrp_ppo {
     PpoNet pn = {};
     float* d_ws = nullptr;        // activations, deltas, terms
     float* d_rows = nullptr;      // row-major image of the hidden weights
-    float* d_vec = nullptr;       // param, grad, m, v (n_params each), coef
+    float* d_vec = nullptr;       // param, grad, m, v (n_params each), coef, the combined approx_kl
     float* d_partial = nullptr;   // [max_chunks][n_params]
     double* d_spart = nullptr;    // [max_chunks][NSTAT]
     int* d_idx = nullptr;         // fwd[n_params], row[n_params]
@@ -579,7 +612,7 @@ int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const fl
                        o->pn.sterm, o->d_partial, P, o->d_spart, words);
     float* g = d_grad ? d_grad : o->grad();
     hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g, words);
-    hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats, words,
+    hipLaunchKernelGGL(k_ppo_norm<false>, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats, words,
                        kl_limit);
     MRP_HIPCHK(o, hipGetLastError());
     return MRP_OK;
@@ -798,6 +831,34 @@ int mrp_ppo_minibatch_device(mrp_ppo* o, void* hip_stream, int B, const long lon
     return ppo_adam_launch(o, st, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps}, o->d_words);
 }
 
+int mrp_ppo_apply_device(mrp_ppo* o, void* hip_stream, int R, const float* d_parts, long long part_stride, double target_kl,
+                         double max_grad_norm, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
+                         float step_size, float eps, float* d_stats) {
+    if (!o) return MRP_E_ARG;
+    const char* who = "mrp_ppo_apply_device";
+    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
+    if (R < 1 || R > 64) return bad("R outside 1..64");
+    if (!d_parts || !d_stats) return bad("null pointer");
+    const int P = o->n_params;
+    if (part_stride < (long long)P + NSTAT) return bad("part_stride < n_params + 5");
+    const size_t f = sizeof(float);
+    if (const char* what = check_outputs({{d_parts, (size_t)R * (size_t)part_stride * f}}, {{d_stats, NSTAT * f}})) return bad(what);
+    mrp_policy* p = o->policy;
+    if (!p->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const int pb = (P + P_NT - 1) / P_NT;
+    if (o->seen_version != p->version) {
+        hipLaunchKernelGGL(k_ppo_import, dim3(pb), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P, o->param(), o->d_rows);
+        o->seen_version = p->version;
+    }
+    hipLaunchKernelGGL(k_ppo_combine, dim3((P + NSTAT + P_NT - 1) / P_NT), dim3(P_NT), 0, st, d_parts, R, (size_t)part_stride, P,
+                       (float)(1.0 / (double)R), o->grad(), d_stats, o->coef() + 1, o->d_words);
+    hipLaunchKernelGGL(k_ppo_norm<true>, dim3(1), dim3(P_NT), 0, st, o->grad(), P, max_grad_norm, nullptr, 0, 0, o->coef(), nullptr,
+                       o->d_words, target_kl < 0.0 ? -1.0 : 1.5 * target_kl);
+    return ppo_adam_launch(o, st, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps}, o->d_words);
+}
+
 int mrp_ppo_progress(mrp_ppo* o, void* hip_stream, int* stopped, int* applied) {
     if (!o) return MRP_E_ARG;
     if (!stopped || !applied) { o->err = "mrp_ppo_progress: null pointer"; return MRP_E_ARG; }
@@ -836,6 +897,16 @@ int mrp_ppo_get_state(mrp_ppo* o, float* m, float* v) {
     MRP_HIPCHK(o, hipDeviceSynchronize());
     MRP_HIPCHK(o, hipMemcpy(m, o->m(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
     MRP_HIPCHK(o, hipMemcpy(v, o->v(), (size_t)o->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    return MRP_OK;
+}
+
+int mrp_ppo_set_state(mrp_ppo* o, const float* m, const float* v) {
+    if (!o) return MRP_E_ARG;
+    if (!m || !v) { o->err = "mrp_ppo_set_state: null pointer"; return MRP_E_ARG; }
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    MRP_HIPCHK(o, hipDeviceSynchronize());
+    MRP_HIPCHK(o, hipMemcpy(o->m(), m, (size_t)o->n_params * sizeof(float), hipMemcpyHostToDevice));
+    MRP_HIPCHK(o, hipMemcpy(o->v(), v, (size_t)o->n_params * sizeof(float), hipMemcpyHostToDevice));
     return MRP_OK;
 }
 

@@ -3,11 +3,16 @@
 Worlds are independent, so the physics never exchanges data between GPUs.
 Rank r owns global lanes [r*L, (r+1)*L) and passes ``lane_offset = r*L`` to ``mrp_create``;
 the device RNG is keyed by the global lane id, so every lane's trajectory is identical at any
-GPU count.  The only collective is the per-step hand-over of (obs, reward, done) to the
+GPU count.  The rollout's only collective is the per-step hand-over of (obs, reward, done) to the
 policy rank: each rank packs them into ONE contiguous float32 buffer [L, obs_dim + 2] (done as
 0.0/1.0) and ``torch.distributed.gather``s it to rank 0 (RCCL turns this into root receives +
 peer sends, one message per peer over its own xGMI link).  With a policy replica on every
 rank use ``all_gather`` instead (``StepGather(..., to_all=True)``).
+
+Training with a policy replica and a rollout buffer on every rank needs one more collective, per
+minibatch: ``GradExchange`` all-gathers every rank's flat gradient and statistics into one ``[R, stride]``
+buffer in rank order, which ``DevicePPO`` combines in that fixed order (``ppo.combine_ref``), so every
+replica applies the same bits.
 """
 from __future__ import annotations
 
@@ -86,3 +91,41 @@ class StepGather:
             full = self.full
         O = self.obs_dim
         return full[:, :O], full[:, O], full[:, O + 1] != 0
+
+
+class GradExchange:
+    """All-gathers one flat float32 block per rank (``DevicePPO``'s gradient before clipping and its five
+    statistics) into ``parts`` ``[world, part_stride]``, row ``r`` from rank ``r``; ``part_stride`` is
+    ``n_floats`` rounded up to a multiple of 64.  The owner writes its block into ``mine`` ``[part_stride]``
+    and calls the exchange; every rank then holds the same ``parts``."""
+
+    def __init__(self, shard: Shard, n_floats: int, device, group=None, host_stage: bool = False, force_collective: bool = False):
+        """On a device backend the collective is ``all_gather_into_tensor(parts, mine)`` on device tensors,
+        asynchronous on the current stream.  ``host_stage``: the collective runs on pinned host buffers (a
+        CPU backend such as gloo), with a synchronous device -> host copy before it and a host -> device
+        copy after it.  ``force_collective``: call the collective at world size 1 too; without it world
+        size 1 only copies ``mine`` into ``parts[0]``."""
+        import torch
+        self.shard, self.n_floats, self.group, self.force_collective = shard, int(n_floats), group, force_collective
+        if self.n_floats < 1:
+            raise ValueError("GradExchange: n_floats must be >= 1")
+        self.world = shard.world
+        self.part_stride = -(-self.n_floats // 64) * 64
+        self.mine = torch.zeros(self.part_stride, dtype=torch.float32, device=device)
+        self.parts = torch.zeros((self.world, self.part_stride), dtype=torch.float32, device=device)
+        self.host_mine = torch.zeros(self.part_stride, dtype=torch.float32).pin_memory() if host_stage else None
+        self.host_parts = torch.zeros((self.world, self.part_stride), dtype=torch.float32).pin_memory() if host_stage else None
+
+    def __call__(self):
+        """Returns ``parts`` with every rank's ``mine`` in rank order, valid until the next call."""
+        if self.world == 1 and not self.force_collective:
+            self.parts[0].copy_(self.mine)
+            return self.parts
+        import torch.distributed as dist
+        if self.host_mine is not None:
+            self.host_mine.copy_(self.mine)   # synchronous device -> pinned host copy: the CPU collective reads it next
+            dist.all_gather_into_tensor(self.host_parts.view(-1), self.host_mine, group=self.group)
+            self.parts.copy_(self.host_parts)
+        else:
+            dist.all_gather_into_tensor(self.parts.view(-1), self.mine, group=self.group)   # flat: rank r's block is row r
+        return self.parts

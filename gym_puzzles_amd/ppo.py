@@ -4,8 +4,8 @@
 write the device policy's parameters in place (``csrc/mrp_ppo.hip``, ``mrp_ppo_*`` in
 ``include/mrp.h``), with no host synchronisation and no atomics.
 
-``ppo_grad_ref``, ``adam_ref``, ``normalize_adv_ref``, ``kl_stop_ref`` and ``ppo_train_ref`` are the numpy
-statement of the rule and the definition the kernels match bit for bit.  Everything is float32 with every operation rounded on its
+``ppo_grad_ref``, ``adam_ref``, ``normalize_adv_ref``, ``kl_stop_ref``, ``ppo_train_ref``, ``combine_ref`` and
+``ppo_train_dist_ref`` are the numpy statement of the rule and the definition the kernels match bit for bit.  Everything is float32 with every operation rounded on its
 own unless stated otherwise; ``B`` is the minibatch size, ``invB = float32(1.0 / B)``.
 
 * ``exp_ref``: this build's float32 exp (``csrc/mrp_math.h`` ``exp_f32``), operation for operation;
@@ -46,7 +46,20 @@ own unless stated otherwise; ``B`` is the minibatch size, ``invB = float32(1.0 /
   returned as it is;
 * ``target_kl`` (``kl_stop_ref``): after a minibatch's statistics, ``float64(approx_kl) > 1.5 *
   float64(target_kl)`` (strict) means that this minibatch is not applied and the whole ``train`` call
-  ends; ``ppo_train_ref`` holds the order.
+  ends; ``ppo_train_ref`` holds the order;
+* data-parallel training (``combine_ref``, ``ppo_train_dist_ref``): ``R`` ranks hold one copy of the
+  parameters and of Adam's state each and a rollout buffer of their own.  For a minibatch every rank ``r``
+  computes ``g_r, s_r = ppo_grad_ref`` on its local minibatch with ``invB = float32(1.0 / B_local)`` (its
+  advantages through ``normalize_adv_ref`` on the local minibatch first, ``clip_range_vf`` as above): the
+  gradient before clipping.  Then ``g = g_0; g = g + g_1; ...; g = g + g_{R-1}`` in ascending rank order,
+  every add a float32 add rounded alone, and ``g = g * float32(1.0 / R)``; the five statistics are combined
+  by the same adds and the same multiply in float32 (all five are means).  At ``R = 1`` this is the
+  identity, signed zeros included.  ``kl_stop_ref`` then decides on the combined ``approx_kl``, and if it
+  does not stop ``clip_coef_ref`` and ``adam_ref`` run on the combined gradient, with the combined row as
+  the statistics row recorded.  The order is fixed and nothing is atomic, so every rank computes the same
+  bits: after any number of minibatches the ranks' parameters, ``std``, moments, ``t`` and ``stopped`` are
+  identical.  The combined gradient is the gradient of the mean of the ranks' losses; it is not, bit for
+  bit, what one rank holding the union minibatch computes (that is another chunk order).
 
 ``DevicePPO(minibatch="device")`` gathers the minibatch and normalises its advantages by this rule in HIP;
 with ``minibatch="torch"`` (the default) the gather is ``index_select`` and ``normalize_advantage`` is
@@ -358,6 +371,70 @@ def ppo_train_ref(params, state, data, epochs, batch_size, *, old_values=None, n
     return params, np.array(stats, _f32).reshape(-1, 5)
 
 
+# ---- data-parallel training --------------------------------------------------------------------------
+def combine_ref(grads, stats):
+    """The ranks' gradients (float32 ``[R, n_params]``) and statistics (float32 ``[R, 5]``), one row per
+    rank in ascending rank order, combined by the rule of the module docstring: ``g = rows[0]``, then ``g = g
+    + rows[r]`` for ``r = 1 .. R - 1`` (float32 adds, each rounded alone), then ``g * float32(1.0 / R)``.
+    Returns ``(grad [n_params], stats [5])``; the identity at ``R = 1``."""
+    grads, stats = np.ascontiguousarray(grads, _f32), np.ascontiguousarray(stats, _f32)
+    if grads.ndim != 2 or grads.shape[0] < 1 or stats.shape != (grads.shape[0], 5):
+        raise ValueError("combine_ref: grads is [R, n_params] and stats [R, 5] with R >= 1")
+    R = grads.shape[0]
+    inv = _f32(1.0 / R)
+
+    def combine(rows):
+        g = rows[0].copy()
+        for r in range(1, R):
+            g = (g + rows[r]).astype(_f32)
+        return (g * inv).astype(_f32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return combine(grads), combine(stats)
+
+
+def ppo_train_dist_ref(params, state, datas, epochs, batch_size, perms, *, old_values=None, normalize_advantage=False,
+                       clip_range_vf=None, target_kl=None, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                       betas=(0.9, 0.999), eps=1e-5):
+    """``ppo_train_ref`` for ``R = len(datas)`` ranks in lockstep.  ``datas[r]`` is rank ``r``'s ``(obs,
+    actions, old_log_probs, advantages, returns)`` (``old_values[r]`` its value predictions for
+    ``clip_range_vf``), ``perms[r]`` its ``epochs`` index arrays (one sample order per epoch).  For every
+    minibatch each rank takes its own rows by its own order, normalises its local advantages with
+    ``normalize_advantage`` and runs ``ppo_grad_ref``; ``combine_ref``'s row is the statistics row recorded;
+    ``kl_stop_ref`` on the combined ``approx_kl`` ends the call for every rank; otherwise the clip and Adam
+    run on the combined gradient.  One ``params`` and one ``state`` serve all ranks.  ``ValueError`` unless
+    every rank has ``epochs`` orders of one common length.  Returns ``(params, stats [n_evaluated, 5])``."""
+    R, epochs, bs = len(datas), int(epochs), int(batch_size)
+    if R < 1 or len(perms) != R or (old_values is not None and len(old_values) != R):
+        raise ValueError("ppo_train_dist_ref: one data tuple, one list of orders (and one old_values) per rank")
+    orders = [[np.asarray(o) for o in p] for p in perms]
+    if any(len(p) != epochs for p in orders) or len({o.size for p in orders for o in p}) > 1:
+        raise ValueError("ppo_train_dist_ref: the ranks' minibatch counts differ (T * N, batch_size and n_epochs must agree)")
+    stats = []
+    stop = False
+    for e in range(epochs):
+        for s in range(0, orders[0][e].size, bs):
+            grads, rows = [], []
+            for r in range(R):
+                idx = orders[r][e][s:s + bs]
+                obs, actions, old_lp, adv, ret = (np.asarray(a)[idx] for a in datas[r])
+                if normalize_advantage:
+                    adv = normalize_adv_ref(adv)
+                g, st = ppo_grad_ref(params, obs, actions, old_lp, adv, ret, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                                     old_values=None if old_values is None else np.asarray(old_values[r])[idx],
+                                     clip_range_vf=clip_range_vf)
+                grads.append(g)
+                rows.append(st)
+            grad, st = combine_ref(np.stack(grads), np.stack(rows))
+            stats.append(st)
+            stop = target_kl is not None and kl_stop_ref(st[3], target_kl)
+            if stop:
+                break
+            params = _apply_ref(params, state, grad, lr, max_grad_norm, betas, eps)
+        if stop:
+            break
+    return params, np.array(stats, _f32).reshape(-1, 5)
+
+
 # ---- the device class --------------------------------------------------------------------------------
 class DevicePPO(Handle):
     """The rule on the device: ``grad`` is ``ppo_grad_ref``, ``step`` is ``ppo_step_ref`` written into
@@ -374,13 +451,20 @@ class DevicePPO(Handle):
     are read back (one ``mrp_ppo_progress``, which synchronises) when first asked for, and the next ``step``
     / ``train`` asks, because Adam's bias correction needs ``t``.  ``minibatch="device"`` gathers each
     minibatch and normalises its advantages (``normalize_adv_ref``) in HIP; ``"torch"`` (the default) is
-    ``index_select`` and torch arithmetic."""
+    ``index_select`` and torch arithmetic.
+
+    Data-parallel training (``combine_ref`` / ``ppo_train_dist_ref``): with ``shard`` (a ``dist.Shard`` of
+    ``world > 1``) or an explicit ``exchange`` (a ``dist.GradExchange`` of ``n_params + 5`` floats) ``train``
+    splits every minibatch in two: the local gradient before clipping and the local statistics go into
+    ``exchange.mine``, the exchange gathers every rank's, and ``mrp_ppo_apply_device`` combines them in rank
+    order and applies the clip, the ``target_kl`` decision and Adam, the same bits on every rank.  Call
+    ``sync_from`` once before training so that the replicas start equal.  ``step`` and ``grad`` stay local."""
 
     _DESTROY, _LAST_ERROR, _VALUE_ERRORS = "mrp_ppo_destroy", "mrp_ppo_last_error", (-1, -3)
 
     def __init__(self, policy, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                  max_grad_norm=0.5, normalize_advantage=True, betas=(0.9, 0.999), eps=1e-5, max_batch=None, clip_range_vf=None,
-                 target_kl=None, minibatch="torch"):
+                 target_kl=None, minibatch="torch", shard=None, exchange=None):
         if minibatch not in ("torch", "device"):
             raise ValueError(f"DevicePPO: minibatch is {minibatch!r}, expected 'torch' or 'device'")
         if clip_range_vf is not None and not clip_range_vf >= 0:
@@ -393,9 +477,16 @@ class DevicePPO(Handle):
         self.clip_range_vf, self.target_kl, self.minibatch = clip_range_vf, target_kl, minibatch
         self.max_batch = int(self.batch_size if max_batch is None else max_batch)
         self._t, self._n_applied, self._stopped, self._pending, self._staged = 0, 0, False, False, None
+        self._base, self._checked = 0, None      # t before a pending train; the (T * N, batch, epochs) the ranks last agreed on
         self.device = policy.device
         self._open("mrp_ppo_create", policy._h, self.max_batch)
         self.n_params = int(self._L.mrp_ppo_n_params(self._h))
+        if exchange is None and shard is not None and shard.world > 1:
+            from .dist import GradExchange
+            exchange = GradExchange(shard, self.n_params + 5, self.device)
+        if exchange is not None and exchange.n_floats < self.n_params + 5:
+            raise ValueError(f"DevicePPO: the exchange holds {exchange.n_floats} floats, n_params + 5 is {self.n_params + 5}")
+        self.exchange = exchange
 
     @property
     def _h(self):
@@ -415,7 +506,7 @@ class DevicePPO(Handle):
         if self._pending:
             self._pending = False         # cleared first: a bad index raises once and leaves t at its base
             self._stopped, self._n_applied = self.progress()
-            self._t += self._n_applied
+            self._t = self._base + self._n_applied
 
     @property
     def t(self):
@@ -546,13 +637,22 @@ class DevicePPO(Handle):
         HIP, one library call per minibatch.  With ``target_kl`` every minibatch is still enqueued; those
         from the stopping one on do nothing on the device and their statistics rows stay zero.
         ``poll=True`` reads ``stopped`` after each epoch (a synchronisation) and stops enqueueing: the
-        results are the same."""
+        results are the same.
+
+        With an exchange (data-parallel training) every minibatch is the local phase into
+        ``exchange.mine``, the exchange, and ``mrp_ppo_apply_device`` (``ppo_train_dist_ref``), in either
+        gather mode.  Every rank must pass the same ``T * N``, ``batch_size`` and ``n_epochs``: they are
+        compared across ranks (one ``all_gather_object``, only when they differ from the last ones
+        compared) and a mismatch raises ``ValueError`` on every rank before anything is enqueued."""
         import torch
         total = buffer.n_steps * buffer.n_lanes
         per_epoch = -(-total // self.batch_size)
         stats = torch.zeros(self.n_epochs * per_epoch, 5, dtype=torch.float32, device=self.device)
         u = 0
-        if self.minibatch == "torch" and self.clip_range_vf is None and self.target_kl is None:
+        ex = self.exchange
+        if ex is not None:
+            self._check_ranks(total)
+        if ex is None and self.minibatch == "torch" and self.clip_range_vf is None and self.target_kl is None:
             for _ in range(self.n_epochs):
                 for obs, actions, _, old_lp, adv, ret in buffer.get(self.batch_size, generator):
                     if self.normalize_advantage and adv.numel() > 1:
@@ -564,6 +664,17 @@ class DevicePPO(Handle):
         self._begin()
         t0, stream, kl = self._t, stream_of(self.device), self.target_kl
         use_v = self.clip_range_vf is not None
+        if ex is None:
+            def run(B, index, rows, ptrs, normalize):
+                self._minibatch(stream, B, index, rows, ptrs, normalize, kl, t0 + u + 1, None, stats[u].data_ptr())
+        else:
+            # the local phase writes the gradient before clipping and the statistics side by side into exchange.mine
+            P = self.n_params
+            local_g, local_s = ex.mine[:P].data_ptr(), ex.mine[P:P + 5].data_ptr()
+
+            def run(B, index, rows, ptrs, normalize):
+                self._minibatch(stream, B, index, rows, ptrs, normalize, None, 1, local_g, local_s)
+                self._apply(stream, ex(), kl, t0 + u + 1, stats[u].data_ptr())
         if self.minibatch == "device":
             obs, actions, values, old_lp, adv, ret = buffer.flat_fields()
             _, rows, ptrs = self._batch(obs.reshape(total, -1), actions, old_lp, adv, ret, values if use_v else None,
@@ -575,23 +686,98 @@ class DevicePPO(Handle):
                     idx = flat[start:start + self.batch_size]
                     if idx.shape[0] > self.max_batch:
                         raise ValueError(f"DevicePPO: a minibatch of {idx.shape[0]} samples, max_batch is {self.max_batch}")
-                    self._minibatch(stream, int(idx.shape[0]), idx.data_ptr(), rows, ptrs, self.normalize_advantage, kl, t0 + u + 1,
-                                    None, stats[u].data_ptr())
+                    run(int(idx.shape[0]), idx.data_ptr(), rows, ptrs, self.normalize_advantage)
                     u += 1
             else:
                 for obs, actions, values, old_lp, adv, ret in buffer.get(self.batch_size, generator):
                     if self.normalize_advantage and adv.numel() > 1:
                         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
                     B, rows, ptrs = self._batch(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, values if use_v else None)
-                    self._minibatch(stream, B, None, rows, ptrs, False, kl, t0 + u + 1, None, stats[u].data_ptr())
+                    run(B, None, rows, ptrs, False)
                     u += 1
             if poll and kl is not None and self.progress()[0]:
                 break
         if kl is None:
             self._t, self._n_applied, self._stopped = t0 + u, u, False
         else:
-            self._pending = True
+            self._base, self._pending = t0, True
         return stats
+
+    # ---- data-parallel training
+    def _check_ranks(self, total):
+        """Every rank must enqueue the same number of minibatches: one ``all_gather_object`` of ``(T * N,
+        batch_size, n_epochs)``, repeated only when the triple changes."""
+        triple = (int(total), self.batch_size, self.n_epochs)
+        if triple == self._checked:
+            return
+        ex = self.exchange
+        if ex.world > 1:
+            import torch.distributed as dist
+            seen = [None] * ex.world
+            dist.all_gather_object(seen, triple, group=ex.group)
+            if any(tuple(t) != tuple(seen[0]) for t in seen):
+                raise ValueError(f"DevicePPO.train: (T * N, batch_size, n_epochs) differs across ranks: {seen}")
+        self._checked = triple
+
+    def _apply(self, stream, parts, target_kl, t, stats):
+        """One ``mrp_ppo_apply_device`` on a checked ``[R, stride]`` tensor; ``t`` is the step this would be."""
+        f, d = ctypes.c_float, ctypes.c_double
+        sc = adam_scalars(t, self.learning_rate, self.betas, self.eps)
+        self._check_rc(self._L.mrp_ppo_apply_device(self._h, stream, int(parts.shape[0]), parts.data_ptr(), int(parts.shape[1]),
+                                                    d(-1.0 if target_kl is None else target_kl), d(self.max_grad_norm),
+                                                    *[f(float(x)) for x in sc], stats))
+
+    def apply(self, parts, stats_out=None):
+        """The apply phase alone (``combine_ref``, then ``kl_stop_ref`` and ``adam_ref`` on the combined
+        values) on ``parts``, a float32 ``[R, stride]`` device tensor whose row ``r`` holds rank ``r``'s flat
+        gradient before clipping in its first ``n_params`` floats and its five statistics behind them
+        (``stride >= n_params + 5``, ``R`` in 1..64).  Returns the combined ``stats [5]`` device tensor
+        (``stats_out`` when given, which may not overlap ``parts``).  Never synchronises.  With
+        ``target_kl`` the decision is the device's: ``t``, ``n_applied`` and ``stopped`` resolve as after
+        ``train``, and a stopped call leaves ``stats_out`` as it was."""
+        import torch
+        if not isinstance(parts, torch.Tensor) or parts.dim() != 2:
+            raise ValueError("DevicePPO.apply: parts must be a [R, stride] CUDA tensor")
+        check_tensor("DevicePPO", "parts", parts, self.device, torch.float32, tuple(parts.shape))
+        st = self._out("stats_out", stats_out, 5)
+        self._begin()
+        t0 = self._t
+        self._apply(stream_of(self.device), parts, self.target_kl, t0 + 1, ptr(st))
+        if self.target_kl is None:
+            self._t, self._n_applied, self._stopped = t0 + 1, 1, False
+        else:
+            self._base, self._pending = t0, True
+        return st
+
+    def set_state(self, m, v, t):
+        """Load Adam's moments (flat float32 ``[n_params]`` host arrays) and the step count: the inverse
+        of ``state()`` and ``t`` (synchronises the device)."""
+        m, v = (np.ascontiguousarray(a, _f32).reshape(-1) for a in (m, v))
+        if m.size != self.n_params or v.size != self.n_params:
+            raise ValueError(f"DevicePPO.set_state: m and v hold {self.n_params} floats each")
+        self._resolve()
+        self._check_rc(self._L.mrp_ppo_set_state(self._h, m.ctypes.data, v.ctypes.data))
+        self._t = int(t)
+
+    def sync_from(self, src=0, group=None):
+        """Broadcast rank ``src``'s flat parameters, ``std``, ``m``, ``v`` and ``t`` and load them on every
+        rank, so that the replicas start equal (synchronises; every rank's policy must hold parameters of
+        the one architecture already).  The tensors travel on the device under an nccl group and on the
+        host otherwise."""
+        import torch
+        import torch.distributed as dist
+        like = self.policy.get_params()
+        m, v = self.state()
+        P, A = self.n_params, self.policy.act_dim
+        buf = torch.from_numpy(np.concatenate([flatten_params(like), like.std, m, v]).astype(_f32))
+        step = torch.tensor([self.t], dtype=torch.int64)
+        if dist.get_backend(group) == "nccl":
+            buf, step = buf.to(self.device), step.to(self.device)
+        dist.broadcast(buf, src, group=group)
+        dist.broadcast(step, src, group=group)
+        a = buf.cpu().numpy()
+        self.policy.set_params(unflatten_params(like, a[:P], std=a[P:P + A].copy()))
+        self.set_state(a[P + A:2 * P + A], a[2 * P + A:], int(step.item()))
 
     def staged(self):
         """Host copies of the staging buffers as the last gathered or device-normalised minibatch left

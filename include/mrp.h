@@ -414,6 +414,24 @@ int mrp_ppo_progress(mrp_ppo* o, void* hip_stream, int* stopped, int* applied);
  * clip_range_vf).  Synchronises the device.  For tests. */
 int mrp_ppo_get_staged(mrp_ppo* o, int B, float* obs, float* actions, float* old_values, float* old_log_probs,
                        float* advantages, float* returns);
+/* ---- Data-parallel PPO: the apply phase.  Every rank computes its minibatch's gradient before clipping and
+ * its statistics (mrp_ppo_minibatch_device with d_grad), the ranks exchange them, and every rank applies the
+ * same combined step, so the replicas stay bit-identical (ppo.combine_ref, ppo.ppo_train_dist_ref).
+ *   d_parts  float32 [R][part_stride]: row r holds rank r's flat gradient in its first n_params floats and
+ *            its five statistics at [n_params, n_params + 5); the rest of a row is padding and is not read.
+ * Three launches under the predicate of mrp_ppo_minibatch_device (every kernel first loads `stopped`; a
+ * skipped call writes nothing, d_stats included): the rows are added in ascending rank order with plain
+ * float32 adds and multiplied by float32(1 / R) into the object's gradient vector and into d_stats [5]; then
+ * the grad-norm clip, the target_kl decision (< 0: none) on the combined approx_kl, and Adam with the scalars
+ * of mrp_ppo_step_device, which advances `applied`.  MRP_E_ARG: R outside 1..64, part_stride < n_params + 5,
+ * a null pointer, d_stats overlapping any of the R * part_stride floats of d_parts; MRP_E_STATE before
+ * mrp_policy_set_params.  No allocation, no synchronisation. */
+int mrp_ppo_apply_device(mrp_ppo* o, void* hip_stream, int R, const float* d_parts, long long part_stride,
+                         double target_kl, double max_grad_norm, float beta1, float one_minus_beta1, float beta2,
+                         float one_minus_beta2, float sqrt_bc2, float step_size, float eps, float* d_stats);
+/* Adam's moments from host arrays of n_params floats each: the inverse of mrp_ppo_get_state (a replica
+ * that starts from another rank's optimiser state, a resumed checkpoint).  Synchronises the device. */
+int mrp_ppo_set_state(mrp_ppo* o, const float* m, const float* v);
 /* Device self-test of the exp rule (mrp_math.h exp_f32) on n host inputs (host output). */
 int mrp_selftest_exp(int device, const float* x, float* out, int n);
 

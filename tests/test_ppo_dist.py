@@ -1,0 +1,302 @@
+"""CPU checks of data-parallel PPO's numpy rule (gym_puzzles_amd/ppo.py combine_ref, ppo_train_dist_ref) and of
+dist.GradExchange: the combine's order and signed zeros, the combined gradient against float64 autograd of
+SB3's loss on the union minibatch, the lockstep loop's bookkeeping, and the exchange on two gloo ranks."""
+from __future__ import annotations
+
+import os
+import queue
+import socket
+import sys
+
+import numpy as np
+import pytest
+from test_ppo import ARCHS, U, majorant, make_batch, make_params, sb3_loss, torch_policy
+from test_ppo_options import TRAIN_BATCH, TRAIN_TOTAL, bits, train_data
+
+from gym_puzzles_amd import policy as P
+from gym_puzzles_amd import ppo as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HP = dict(clip_range=0.2, ent_coef=0.01, vf_coef=0.5)
+BIG = np.float32(2.0 ** 60)
+
+
+# ---- combine_ref -------------------------------------------------------------------------------------
+def _by_hand(rows):
+    """The rule with every add written out on numpy float32 scalars."""
+    rows = np.asarray(rows, np.float32)
+    out = np.zeros(rows.shape[1], np.float32)
+    for e in range(rows.shape[1]):
+        g = rows[0, e]
+        for r in range(1, rows.shape[0]):
+            g = np.float32(g + rows[r, e])
+        out[e] = np.float32(g * np.float32(1.0 / rows.shape[0]))
+    return out
+
+
+@pytest.mark.parametrize("ranks", (1, 2, 3, 4))
+def test_combine_ref_is_the_rule(ranks):
+    rng = np.random.default_rng(ranks)
+    grads = (rng.standard_normal((ranks, 301)) * np.logspace(-6, 6, 301)).astype(np.float32)
+    stats = rng.standard_normal((ranks, 5)).astype(np.float32)
+    g, s = R.combine_ref(grads, stats)
+    assert g.dtype == np.float32 and s.dtype == np.float32 and g.shape == (301,) and s.shape == (5,)
+    assert np.array_equal(bits(g), bits(_by_hand(grads))) and np.array_equal(bits(s), bits(_by_hand(stats)))
+    if ranks == 1:
+        assert np.array_equal(bits(g), bits(grads[0])) and np.array_equal(bits(s), bits(stats[0]))
+
+
+def test_combine_ref_identity_at_one_rank_keeps_signed_zeros():
+    row = np.float32([[0.0, -0.0, 1.5, -2.25e-40, 3e38]])
+    g, s = R.combine_ref(row, row)
+    assert np.array_equal(bits(g), bits(row[0])) and np.array_equal(bits(s), bits(row[0]))
+    assert np.signbit(g[1]) and not np.signbit(g[0])
+    assert g is not row and not np.shares_memory(g, row)
+
+
+def test_combine_ref_order_and_signed_zeros():
+    """Rows holding +2^60, 1, -2^60 in different rank orders give different bits: (2^60 + 1) - 2^60 is 0,
+    (2^60 - 2^60) + 1 is 1.  -0 + -0 stays -0 through the multiply; x + -x is +0."""
+    z = np.zeros((3, 5), np.float32)
+    a = R.combine_ref(np.float32([[BIG], [1.0], [-BIG]]), z)[0]
+    b = R.combine_ref(np.float32([[BIG], [-BIG], [1.0]]), z)[0]
+    c = R.combine_ref(np.float32([[1.0], [-BIG], [BIG]]), z)[0]
+    assert a[0] == 0 and b[0] == np.float32(1.0) * np.float32(1.0 / 3) and c[0] == 0
+    assert not np.array_equal(bits(a), bits(b))
+    for ranks in (2, 3, 4):
+        rows = np.zeros((ranks, 2), np.float32)
+        rows[:, 0] = -0.0
+        rows[0, 1], rows[1, 1] = 7.5, -7.5
+        g, s = R.combine_ref(rows, np.full((ranks, 5), -0.0, np.float32))
+        assert g[0] == 0 and np.signbit(g[0]), "-0 + -0 stays -0 through the multiply"
+        assert g[1] == 0 and not np.signbit(g[1]), "x + -x gives +0"
+        assert np.signbit(s).all()
+    with pytest.raises(ValueError):
+        R.combine_ref(np.zeros((2, 4), np.float32), np.zeros((3, 5), np.float32))
+    with pytest.raises(ValueError):
+        R.combine_ref(np.zeros((0, 4), np.float32), np.zeros((0, 5), np.float32))
+
+
+# ---- is it data-parallel PPO? ------------------------------------------------------------------------
+@pytest.mark.parametrize("B", (1, 33))
+@pytest.mark.parametrize("ranks", (2, 4))
+@pytest.mark.parametrize("name", list(ARCHS))
+def test_combined_gradient_is_ppo_on_the_union(name, ranks, B):
+    """combine_ref of the ranks' ppo_grad_ref (no advantage normalisation) against float64 autograd of SB3's
+    loss on the union minibatch.  The bound is a priori: the union's gradient is the mean of the ranks'
+    (equal local sizes), so the ranks' own errors enter as the mean of their bounds (tests/test_ppo.py's
+    (n_bwd + amp * n_fwd) * U * majorant, per rank); each of the R - 1 float32 adds rounds a partial sum that
+    is at most sum_r |g_r| in size, which after the division by R is (R - 1) * U * sum_r |g_r| / R; the
+    multiply by 1 / R is exact for a power of two and one more relative U otherwise."""
+    params = make_params(ARCHS[name], seed=3)
+    batches = [make_batch(params, B, seed=5 + 7 * r) for r in range(ranks)]
+    local = [R.ppo_grad_ref(params, *b, **HP) for b in batches]
+    grads, stats = np.stack([g for g, _ in local]), np.stack([s for _, s in local])
+    got, got_stats = R.combine_ref(grads, stats)
+    union = tuple(np.concatenate([b[i] for b in batches]) for i in range(5))
+    model = torch_policy(params)
+    loss, want_stats, _ = sb3_loss(model, union, HP["clip_range"], HP["ent_coef"], HP["vf_coef"])
+    loss.backward()
+    want = np.concatenate([p.grad.numpy().ravel() for p in model.parameters()])
+    rank_bounds = []
+    for b in batches:
+        maj, _, n_ops = majorant(params, b, HP["clip_range"], HP["ent_coef"], HP["vf_coef"])
+        rank_bounds.append(n_ops * U * maj)
+    bound = np.mean(rank_bounds, axis=0) + (ranks - 1) * U * np.abs(grads.astype(np.float64)).sum(0) / ranks
+    if np.float32(1.0 / ranks) != 1.0 / ranks:
+        bound = bound + U * np.abs(want)
+    err = np.abs(got.astype(np.float64) - want)
+    worst = (err / np.maximum(bound, 1e-300)).max()
+    print(f"{name} R={ranks} B_local={B}: max |grad error| {err.max():.3e}, max error / bound {worst:.4f}")
+    assert (err <= bound).all()
+    # the planted mistake: every rank divides by R * B as well as the combine by R, so the result is 1 / R of the gradient
+    model.zero_grad()
+    (sb3_loss(model, union, HP["clip_range"], HP["ent_coef"], HP["vf_coef"])[0] / ranks).backward()
+    mistaken = np.concatenate([p.grad.numpy().ravel() for p in model.parameters()])
+    excess = (np.abs(want - mistaken) / np.maximum(bound, 1e-300)).max()
+    print(f"{name} R={ranks} B_local={B}: planted division by R * B in each rank: max |difference| / bound {excess:.1f}")
+    assert excess > 2
+    # the statistics row is the mean of the ranks' rows by the same adds: R - 1 roundings of a partial sum
+    s64 = stats.astype(np.float64)
+    s_bound = (ranks - 1) * U * np.abs(s64).sum(0) / ranks
+    assert (np.abs(got_stats.astype(np.float64) - s64.mean(0)) <= s_bound).all()
+    assert abs(s64.mean(0)[4] - want_stats[4]) <= U, "equal local sizes: the mean of the ranks' clip fractions is the union's"
+
+
+# ---- ppo_train_dist_ref ------------------------------------------------------------------------------
+def test_train_dist_ref_one_rank_is_train_ref():
+    d = train_data()
+    n = R.flatten_params(d["params"]).size
+    kw = dict(lr=1e-3, normalize_advantage=True, ent_coef=0.01)
+    s_a, s_b = R.AdamState(n), R.AdamState(n)
+    epochs = [e[:2 * TRAIN_BATCH + 40] for e in d["epochs"]]           # 128 + 128 + 40 per epoch
+    a, sa = R.ppo_train_ref(d["params"], s_a, d["data"], epochs, TRAIN_BATCH, **kw)
+    b, sb = R.ppo_train_dist_ref(d["params"], s_b, [d["data"]], len(epochs), TRAIN_BATCH, [epochs], **kw)
+    assert sa.shape == (6, 5) and s_a.t == s_b.t == 6
+    assert np.array_equal(bits(sa), bits(sb))
+    assert np.array_equal(bits(R.flatten_params(a)), bits(R.flatten_params(b))) and np.array_equal(bits(a.std), bits(b.std))
+    assert np.array_equal(bits(s_a.m), bits(s_b.m)) and np.array_equal(bits(s_a.v), bits(s_b.v))
+
+
+def _two_rank_case():
+    """Two ranks' data on sb3-default parameters: 100 samples each whose old log-probs are the policy's own
+    (the first minibatch's approx_kl is exactly 0 on every rank), and two epochs' orders per rank."""
+    params = make_params(ARCHS["sb3-default"], seed=3)
+    datas, perms = [], []
+    for r in range(2):
+        rng = np.random.default_rng(40 + r)
+        obs = rng.standard_normal((100, params.obs_dim)).astype(np.float32)
+        eps = rng.standard_normal((100, params.act_dim)).astype(np.float32)
+        actions, _, values, lp = P.policy_ref(params, obs, eps)
+        adv = rng.standard_normal(100).astype(np.float32)
+        ret = (values + rng.standard_normal(100)).astype(np.float32)
+        datas.append((obs, actions, lp, adv, ret))
+        perms.append([rng.permutation(100) for _ in range(2)])
+    return params, datas, perms
+
+
+def test_train_dist_ref_target_kl_stops_both_ranks_mid_epoch():
+    """32 + 32 + 32 + 4 samples per epoch and rank.  The loop by hand: `stop` combined steps, then one
+    evaluation on both ranks that is recorded and not applied; nothing runs after it on either rank."""
+    params, datas, perms = _two_rank_case()
+    n = R.flatten_params(params).size
+    lr, target_kl, bs = 1e-3, 0.008, 32
+    state = R.AdamState(n)
+    got, stats = R.ppo_train_dist_ref(params, state, datas, 2, bs, perms, target_kl=target_kl, lr=lr, **HP)
+    stop = stats.shape[0] - 1
+    print(f"two ranks: stops at minibatch {stop} of 8, combined approx_kl {stats[:, 3]}")
+    assert stats[0, 3] == 0 and 0 < stop < 7 and stop % 4 != 0, "mid-epoch, after the first and before the last minibatch"
+    assert R.kl_stop_ref(stats[stop, 3], target_kl) and not any(R.kl_stop_ref(k, target_kl) for k in stats[:stop, 3])
+    assert state.t == stop
+    st2, cur, k = R.AdamState(n), params, 0
+    for e in range(2):
+        for s in range(0, 100, bs):
+            if k > stop:
+                break
+            local = [R.ppo_grad_ref(cur, *(a[perms[r][e][s:s + bs]] for a in datas[r]), **HP) for r in range(2)]
+            g, row = R.combine_ref(np.stack([x[0] for x in local]), np.stack([x[1] for x in local]))
+            assert np.array_equal(bits(row), bits(stats[k])), k
+            if k < stop:
+                flat, _ = R.adam_ref(R.flatten_params(cur), g, st2, lr, 0.5)
+                cur = R.unflatten_params(cur, flat, std=R.exp_ref(flat[:cur.act_dim]))
+            k += 1
+    assert k == stop + 1 and st2.t == stop
+    assert np.array_equal(bits(R.flatten_params(cur)), bits(R.flatten_params(got))) and np.array_equal(bits(cur.std), bits(got.std))
+    assert np.array_equal(bits(st2.m), bits(state.m)) and np.array_equal(bits(st2.v), bits(state.v))
+    # the two ranks' minibatches differ, and either rank alone would have gone another way
+    alone, _ = R.ppo_train_dist_ref(params, R.AdamState(n), datas[:1], 2, bs, perms[:1], target_kl=target_kl, lr=lr, **HP)
+    assert not np.array_equal(bits(R.flatten_params(alone)), bits(R.flatten_params(got)))
+
+
+def test_train_dist_ref_unequal_minibatch_counts_raise():
+    params, datas, perms = _two_rank_case()
+    n = R.flatten_params(params).size
+    with pytest.raises(ValueError, match="minibatch counts"):
+        R.ppo_train_dist_ref(params, R.AdamState(n), datas, 2, 32, [perms[0], [p[:90] for p in perms[1]]])
+    with pytest.raises(ValueError, match="minibatch counts"):
+        R.ppo_train_dist_ref(params, R.AdamState(n), datas, 2, 32, [perms[0], perms[1][:1]])
+    with pytest.raises(ValueError):
+        R.ppo_train_dist_ref(params, R.AdamState(n), datas, 2, 32, perms[:1])
+
+
+# ---- GradExchange ------------------------------------------------------------------------------------
+N_FLOATS = 70          # part_stride 128: the pad behind a rank's block travels too and stays zero
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _block(rank):
+    return (np.arange(N_FLOATS, dtype=np.float32) + 1) * np.float32(rank + 1)
+
+
+def _worker(rank, world, port, force, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch
+    import torch.distributed as dist
+
+    from gym_puzzles_amd.dist import GradExchange, Shard
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        ex = GradExchange(Shard(rank, world, 4), N_FLOATS, "cpu", force_collective=force)
+        calls = []
+        real = dist.all_gather_into_tensor
+
+        def spy(*a, **k):
+            calls.append(1)
+            return real(*a, **k)
+        dist.all_gather_into_tensor = spy
+        for round_ in range(2):                       # a second call overwrites the first one's rows
+            ex.mine[:N_FLOATS].copy_(torch.from_numpy(_block(rank) + round_))
+            parts = ex()
+        assert parts is ex.parts and calls == [1, 1], "the collective runs once per call"
+        q.put((rank, ex.part_stride, parts.numpy().copy()))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def _spawn(world, force):
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, force, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    results = []
+    while len(results) < world:                     # a rank that died ends the wait at once
+        try:
+            results.append(q.get(timeout=0.2))
+        except queue.Empty:
+            assert all(p.is_alive() or p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    return results
+
+
+def test_grad_exchange_two_gloo_ranks():
+    results = _spawn(2, False)
+    assert sorted(r for r, _, _ in results) == [0, 1]
+    for _, stride, parts in results:
+        assert stride == 128 and parts.shape == (2, 128)
+        for r in range(2):
+            assert np.array_equal(parts[r, :N_FLOATS], _block(r) + 1), "every rank holds both rows in rank order"
+            assert not parts[r, N_FLOATS:].any()
+
+
+def test_grad_exchange_world_one():
+    import torch
+
+    from gym_puzzles_amd.dist import GradExchange, Shard
+    ex = GradExchange(Shard(0, 1, 4), N_FLOATS, "cpu")           # copy only: no process group exists here
+    ex.mine[:N_FLOATS].copy_(torch.from_numpy(_block(0)))
+    parts = ex()
+    assert parts is ex.parts and tuple(parts.shape) == (1, 128) and ex.part_stride == 128 and ex.world == 1
+    assert np.array_equal(parts[0, :N_FLOATS].numpy(), _block(0)) and not parts[0, N_FLOATS:].any()
+    assert GradExchange(Shard(0, 1, 4), 64, "cpu").part_stride == 64 and GradExchange(Shard(0, 1, 4), 65, "cpu").part_stride == 128
+    with pytest.raises(ValueError):
+        GradExchange(Shard(0, 1, 4), 0, "cpu")
+    (rank, stride, forced), = _spawn(1, True)                       # the collective itself at world size 1
+    assert rank == 0 and stride == 128 and np.array_equal(forced[0, :N_FLOATS], _block(0) + 1)
+
+
+def test_names_and_abi_of_the_dist_path():
+    import gym_puzzles_amd as G
+    from gym_puzzles_amd import _native
+    from gym_puzzles_amd import dist as D
+    for name in ("combine_ref", "ppo_train_dist_ref"):
+        assert hasattr(G, name)
+    for name in ("mrp_ppo_apply_device", "mrp_ppo_set_state"):
+        assert name in _native.EXPORTED, name
+    assert hasattr(D, "GradExchange") and hasattr(D, "StepGather")
+    for name in ("apply", "set_state", "sync_from"):
+        assert callable(getattr(R.DevicePPO, name))
+    assert TRAIN_TOTAL == 600
