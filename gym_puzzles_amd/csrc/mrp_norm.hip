@@ -15,8 +15,10 @@
 //   Monitor: per lane ep_return += reward (float64, in step order), ep_len += 1; on done both
 //   are reported and restarted.
 // The batch moments are float64 (two passes over the lanes); numpy's float32 np.mean/np.var
-// of a float32 batch round differently, so parity with the restatement is to a stated
-// tolerance (tests/test_norm.py), not bitwise.  Monitor sums are bit-exact.
+// of a float32 batch round differently, so the statistics are held to a bound derived from the
+// inputs around the exact moments and the outputs to half a float32 ulp plus what that bound
+// propagates (tests/vecnorm_exact.py, tests/test_norm_gpu.py), not bitwise.  Counts and Monitor
+// sums are bit-exact; a NaN input gives NaN where numpy's rule does.
 //
 // Kernels: k_moments (one block per statistic column: the D obs columns, plus one block that
 // advances the per-lane discounted returns and takes their moments) and k_apply (one thread per
@@ -49,6 +51,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     __syncthreads();
     return r;
 }
+
+// np.clip(x, -c, c): +-inf saturate and NaN stays NaN (fmin / fmax would return the bound for a NaN)
+__device__ __forceinline__ double clip_np(double x, double c) { return x < -c ? -c : (x > c ? c : x); }
 
 // Chan et al. merge of the batch moments (mean, var over n) into the running (mean, var, count)
 __device__ __forceinline__ void rms_merge(double* mean, double* var, double* count, double bm, double bv, double n) {
@@ -117,10 +122,10 @@ __global__ __launch_bounds__(NT) void k_apply(const float* __restrict__ obs, con
         const int l = e / D, j = e - l * D;
         const double sd = sqrt(obs_var[j] + eps);
         double x = ((double)obs[e] - obs_mean[j]) / sd;
-        obs_out[e] = (float)fmin(fmax(x, -clip_obs), clip_obs);
+        obs_out[e] = (float)clip_np(x, clip_obs);
         if (step && done && done[l] && term && term_out) {
             double y = ((double)term[e] - obs_mean[j]) / sd;
-            term_out[e] = (float)fmin(fmax(y, -clip_obs), clip_obs);
+            term_out[e] = (float)clip_np(y, clip_obs);
         }
     }
     if (e >= L) return;
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(NT) void k_apply(const float* __restrict__ obs, con
     const double r = (double)reward[l];
     if (reward_out) {
         double x = r / sqrt(ret_stats[1] + eps);
-        reward_out[l] = (float)fmin(fmax(x, -clip_rew), clip_rew);
+        reward_out[l] = (float)clip_np(x, clip_rew);
     }
     // Monitor sums the env's own (float64) rewards when the step exported them
     double er = ep_ret[l] + (reward64 ? reward64[l] : r);

@@ -258,7 +258,15 @@ class DeviceVecNormalize(Handle):
     env in ``VecNormalize`` with default arguments (``train/train.py:68,80-82``).  All arrays are
     contiguous torch CUDA tensors on ``device``, float32 unless stated; ``reset`` and ``step`` raise
     ``ValueError`` for any other tensor before anything is launched.  The kernels are element-wise, so
-    an output may be its input (``obs_out is obs``).  Calls are asynchronous on the current torch stream."""
+    an output may be its input (``obs_out is obs``, ``reward_out is reward``, ``term_out is term_obs``).  Calls
+    are asynchronous on the current torch stream.
+
+    Contract (tests/vecnorm_exact.py, tests/test_norm_gpu.py): the statistics are within a bound derived
+    from the inputs of the exact batch moments and merge; a float32 output is within half a float32 ulp of
+    the exact value plus what that bound propagates, and exactly ``float32(+-clip)`` where saturated; counts
+    and Monitor's returns and lengths are bit-exact; ``term_out``, ``ep_return`` and ``ep_len`` are written
+    for done lanes only; NaN propagates as in numpy (a NaN observation makes its column's statistics and
+    outputs NaN from then on, ``+-inf`` saturates)."""
 
     _DESTROY, _LAST_ERROR = "mrp_norm_destroy", "mrp_norm_last_error"
 

@@ -68,8 +68,9 @@ class VecNormalizeRef:
         self.ep_len[:] = 0
         return self.normalize_obs(obs)
 
-    def step(self, obs, reward, done, term_obs=None):
-        """Returns (obs', reward', term_obs' for done lanes or None, episode returns, lengths for done lanes)."""
+    def step(self, obs, reward, done, term_obs=None, reward64=None):
+        """Returns (obs', reward', term_obs' for done lanes or None, episode returns, lengths for done lanes).
+        ``reward64``: the env's float64 rewards, which Monitor then sums in place of the float32 ones."""
         done = np.asarray(done).astype(bool)
         if self.training and self.norm_obs:
             self.obs_rms.update(obs)
@@ -79,7 +80,7 @@ class VecNormalizeRef:
             self.ret_rms.update(self.returns)
         r = self.normalize_reward(reward)
         t = self.normalize_obs(term_obs) if term_obs is not None else None
-        self.ep_ret += np.asarray(reward, np.float64)
+        self.ep_ret += np.asarray(reward if reward64 is None else reward64, np.float64)
         self.ep_len += 1
         er, el = self.ep_ret.copy(), self.ep_len.copy()
         self.ep_ret[done] = 0.0

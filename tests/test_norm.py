@@ -1,11 +1,18 @@
-"""On-device VecNormalize + Monitor statistics (mrp_norm.hip) against the numpy
+"""On-device VecNormalize + Monitor statistics (mrp_norm.hip) and the numpy
 restatement of stable-baselines3's algorithm (oracle/vecnorm_ref.py; SB3 is not installed, so
 parity with SB3 itself is unpinned).
 
-Tolerances: batch moments are float64 on both sides but summed in a different order (a
-256-thread tree on the device, numpy's pairwise sum here), so statistics agree to rtol 1e-12 and
-normalised float32 outputs to 2 ulp-scale (rtol 1e-6, atol 1e-6).  Monitor episode returns are
-sequential float64 sums of the same float32 rewards in the same order: bit-exact.
+The contract (tests/vecnorm_exact.py: the rule over Fractions, bounds derived from the inputs):
+statistics within the derived bound of the exact moments, float32 outputs within half a float32
+ulp of the exact value plus the propagated bound, counts and Monitor bit-exact, NaN propagated as
+numpy does.  Here, on the CPU, the restatement is held to it and deliberately wrong variants of
+it are shown to be rejected; tests/test_norm_gpu.py holds the device to it on the same inputs.
+
+The env-driven GPU tests below cover the wiring with Batch at 1024 lanes of v0 and compare the
+device with the restatement: batch moments are float64 on both sides but summed in a different
+order (a 256-thread tree on the device, row after row in numpy), so statistics agree to rtol 1e-10
+and normalised float32 outputs to 2 ulp-scale (rtol 1e-6, atol 1e-6) there.  Monitor episode
+returns are sequential float64 sums of the same rewards in the same order: bit-exact.
 """
 from __future__ import annotations
 
@@ -289,3 +296,183 @@ def test_device_vecnormalize_refuses_wrong_tensors_before_any_launch(gpu_lib):
     assert norm.get_stats()["ret_count"] > before["ret_count"]
     norm.close()
     b.close()
+
+
+# ---- the exact rule (tests/vecnorm_exact.py): the restatement passes it, wrong rules do not ---------------
+
+def _exact():
+    import vecnorm_exact
+    return vecnorm_exact
+
+
+def _clips(args):
+    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
+
+
+def _runs():
+    """(id, inputs, constructor arguments, script, exact records) of every case and scenario."""
+    ve = _exact()
+    for i, c in enumerate(ve.CASES):
+        yield ve.case_id(c), ve.case_inputs(i), ve.ARGS[c[2]], ve.plain_script(), ve.exact_case(i)
+    for name in ve.SCENARIOS:
+        inputs, args, script = ve.scenario(name)
+        yield name, inputs, args, script, ve.exact_scenario(name)
+
+
+def test_restatement_is_within_the_exact_bounds():
+    """oracle/vecnorm_ref.py, a correct float64 implementation, passes the checkers on every case with
+    the statistics below half their bound (the device gets the same room); an output's bound is mostly
+    the half ulp of its own float32 rounding, so there the limit is the bound itself."""
+    from oracle.vecnorm_ref import VecNormalizeRef
+    ve = _exact()
+    worst = dict.fromkeys(ve.RATIO_KEYS, 0.0)
+    for name, inputs, args, script, exact in _runs():
+        got = ve.run_script(ve.RefAdapter(VecNormalizeRef(inputs["L"], inputs["D"], **args)), inputs, script)
+        w = ve.judge(got, exact, *_clips(args), where=name)
+        worst = {k: max(worst[k], w[k]) for k in worst}
+    print("restatement, worst error / bound:", {k: float(f"{v:.3g}") for k, v in worst.items()})
+    for k in ("obs_mean", "obs_var", "ret_mean", "ret_var", "obs_slack", "reward_slack", "term_slack"):
+        assert worst[k] < 0.5, (k, worst[k])
+
+
+def _wrong_rms(kind):
+    from oracle.vecnorm_ref import RunningMeanStd
+    f32 = np.float32
+
+    class Wrong(RunningMeanStd):
+        def update(self, x):
+            x = np.asarray(x, np.float64)
+            n = x.shape[0]
+            xs = x[:-1] if kind == "last lane dropped" or (kind == "last lane dropped at L % 256 == 1" and n % 256 == 1) else x
+            if kind == "float32 sums":
+                x32 = x.astype(f32)
+                bm32 = x32.sum(axis=0, dtype=f32) / f32(n)
+                bm, bv = np.asarray(bm32, np.float64), np.asarray(((x32 - bm32) ** 2).sum(axis=0, dtype=f32) / f32(n), np.float64)
+            else:
+                bm = xs.sum(axis=0) / n
+                if kind == "one-pass variance":
+                    bv = (xs * xs).sum(axis=0) / n - bm * bm
+                else:
+                    bv = ((xs - bm) ** 2).sum(axis=0) / (n - 1 if kind == "sample variance" else n)
+            delta = bm - self.mean
+            tot = self.count + n
+            c = tot if kind == "post-update count in the merge" else self.count
+            new_mean = self.mean + delta * n / tot
+            m2 = self.var * c + bv * n + delta * delta * c * n / tot
+            self.mean, self.var, self.count = new_mean, m2 / tot, tot
+    return Wrong
+
+
+def _wrong_vec(kind):
+    from oracle.vecnorm_ref import VecNormalizeRef
+    f32 = np.float32
+
+    class Wrong(VecNormalizeRef):
+        def normalize_obs(self, obs):
+            if kind == "eps outside the square root":
+                x = (np.asarray(obs, np.float64) - self.obs_rms.mean) / (np.sqrt(self.obs_rms.var) + self.epsilon)
+                return np.clip(x, -self.clip_obs, self.clip_obs).astype(f32)
+            if kind == "clip after the float32 cast":
+                x = (np.asarray(obs, np.float64) - self.obs_rms.mean) / np.sqrt(self.obs_rms.var + self.epsilon)
+                return np.clip(x.astype(f32), -f32(self.clip_obs), f32(self.clip_obs))
+            return super().normalize_obs(obs)
+
+        def normalize_reward(self, r):
+            if kind == "eps outside the square root":
+                x = np.asarray(r, np.float64) / (np.sqrt(self.ret_rms.var) + self.epsilon)
+                return np.clip(x, -self.clip_reward, self.clip_reward).astype(f32)
+            if kind == "clip after the float32 cast":
+                x = np.asarray(r, np.float64) / np.sqrt(self.ret_rms.var + self.epsilon)
+                return np.clip(x.astype(f32), -f32(self.clip_reward), f32(self.clip_reward))
+            return super().normalize_reward(r)
+
+        def step(self, obs, reward, done, term_obs=None, reward64=None):
+            stale_term = self.normalize_obs(term_obs) if term_obs is not None else None
+            advanced = self.returns * self.gamma + np.asarray(reward, np.float64)
+            if kind == "returns advanced in evaluation mode" and not self.training:
+                self.returns = advanced
+            o, r, t, er, el = super().step(obs, reward, done, term_obs, reward64)
+            if kind == "returns not zeroed on done" and self.training:
+                self.returns = advanced
+            if kind == "terminal obs with the pre-update statistics":
+                t = stale_term
+            return o, r, t, er, el
+    return Wrong
+
+
+_WRONG_RMS = ("one-pass variance", "float32 sums", "last lane dropped", "last lane dropped at L % 256 == 1",
+              "sample variance", "post-update count in the merge")
+_WRONG_VEC = ("eps outside the square root", "returns not zeroed on done", "returns advanced in evaluation mode",
+              "terminal obs with the pre-update statistics")
+
+
+def _make_wrong(kind, L, D, args):
+    from oracle.vecnorm_ref import VecNormalizeRef
+    if kind in _WRONG_RMS:
+        n, rms = VecNormalizeRef(L, D, **args), _wrong_rms(kind)
+        n.obs_rms, n.ret_rms = rms((D,)), rms(())
+        return n
+    return _wrong_vec(kind)(L, D, **args)
+
+
+@pytest.mark.parametrize("kind", _WRONG_RMS + _WRONG_VEC)
+def test_checkers_reject_a_wrong_rule(kind):
+    """Each deliberately wrong variant of the restatement is rejected on at least one case: the inputs
+    and bounds of tests/vecnorm_exact.py leave none of these mistakes room to hide."""
+    ve = _exact()
+    rejected = []
+    for name, inputs, args, script, exact in _runs():
+        got = ve.run_script(ve.RefAdapter(_make_wrong(kind, inputs["L"], inputs["D"], args)), inputs, script)
+        w = ve.judge(got, exact, *_clips(args), fail=False, where=name)
+        if max(w[k] for k in w if not k.endswith("_slack")) > 1.0:
+            rejected.append(name)
+    print(f"{kind}: rejected on {len(rejected)} runs: {rejected}")
+    assert rejected, f"the checkers let '{kind}' through on every case"
+
+
+def test_clip_after_the_float32_cast_is_the_same_rule():
+    """Rounding to float32 is monotonic, so float32(min(max(x, -c), c)) == min(max(float32(x), -float32(c)),
+    float32(c)) for every x and c: clipping after the cast with a float32 threshold differs nowhere and is
+    not a wrong rule.  Pinned here bit for bit (clip thresholds 10, 2 and 0.5, and 0.1, which float32
+    does not hold), so that nobody looks for a rejection that cannot exist."""
+    from oracle.vecnorm_ref import VecNormalizeRef
+    ve = _exact()
+    runs = list(_runs())
+    name, inputs, _, script, _ = runs[4]
+    runs.append((name + "-clip0.1", inputs, {"clip_obs": 0.1, "clip_reward": 0.1}, script, None))
+    for name, inputs, args, script, _ in runs:
+        a = ve.run_script(ve.RefAdapter(VecNormalizeRef(inputs["L"], inputs["D"], **args)), inputs, script)
+        wrong = _make_wrong("clip after the float32 cast", inputs["L"], inputs["D"], args)
+        b = ve.run_script(ve.RefAdapter(wrong), inputs, script)
+        for x, y in zip(a, b):
+            for k in ("obs_out", "reward_out", "term_out"):
+                if x.get(k) is not None:
+                    np.testing.assert_array_equal(x[k].view(np.uint32), y[k].view(np.uint32), err_msg=f"{name} {k}")
+
+
+def test_restatement_propagates_nan_like_numpy():
+    """np.clip returns NaN for NaN and saturates +-inf.  A NaN (or an inf, whose variance is inf - inf)
+    poisons its column's statistics, so that column is NaN in every lane from that step on and
+    nothing else is; a NaN reward does the same to the return statistics and every later reward."""
+    from oracle.vecnorm_ref import VecNormalizeRef
+    ve = _exact()
+    assert np.isnan(np.clip(np.nan, -1, 1)) and np.clip(np.inf, -1, 1) == 1 and np.clip(-np.inf, -1, 1) == -1
+    inputs = ve.nonfinite_inputs()
+    ref = VecNormalizeRef(65, 3)
+    got = ve.run_script(ve.RefAdapter(ref), inputs, ve.plain_script())
+    for t, g in enumerate(got):          # call 0 is the reset, call t is step t
+        cols = [c for c, first in ((1, 2), (2, 3)) if t >= first]
+        want = np.zeros((65, 3), bool)
+        want[:, cols] = True
+        np.testing.assert_array_equal(np.isnan(g["obs_out"]), want, err_msg=f"obs_out @{t}")
+        np.testing.assert_array_equal(np.isnan(g["stats"]["obs_mean"]) | np.isinf(g["stats"]["obs_mean"]), want[0])
+        np.testing.assert_array_equal(np.isnan(g["stats"]["obs_var"]), want[0])
+        if t:
+            np.testing.assert_array_equal(np.isnan(g["term_out"]), want, err_msg=f"term_out @{t}")
+            np.testing.assert_array_equal(np.isnan(g["reward_out"]), np.full(65, t >= 4), err_msg=f"reward_out @{t}")
+            assert np.isnan(g["stats"]["ret_mean"]) == np.isnan(g["stats"]["ret_var"]) == (t >= 4)
+    # Monitor: the lane's episode sum is NaN from the NaN reward until the lane is done
+    lane, alive = 64, True
+    for t in range(4, 7):
+        assert np.isnan(got[t]["ep_return"][lane]) == alive and not np.isnan(np.delete(got[t]["ep_return"], lane)).any()
+        alive = alive and not inputs["steps"][t - 1]["done"][lane]
