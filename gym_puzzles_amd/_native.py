@@ -87,6 +87,9 @@ ABI = {
     "mrp_norm_reset_device": (_i, [_P, _P, _P]),
     "mrp_norm_step_device": (_i, [_P] * 10),
     "mrp_norm_step_device_ex": (_i, [_P] * 11),
+    "mrp_norm_part_len": (_i, [_i]),
+    "mrp_norm_local_device": (_i, [_P, _P, _P, _i, _P]),
+    "mrp_norm_apply_device": (_i, [_P, _i, _P, ctypes.c_longlong, _i] + [_P] * 10),
     "mrp_norm_get_stats": (_i, [_P, _P]),
     "mrp_norm_set_stats": (_i, [_P, _P]),
     "mrp_gae_device": (_i, [_i, _P, _i, _i] + [_P] * 7 + [_d, _d, _P, _P]),

@@ -24,6 +24,9 @@
 // advances the per-lane discounted returns and takes their moments) and k_apply (one thread per
 // obs element for the normalised obs / terminal obs; per lane: reward, returns reset, Monitor).
 // Both are tiny next to k_step; the statistics stay on the device between steps.
+// Data-parallel (one set of statistics over the lanes of all ranks, DESIGN.md "Data-parallel
+// VecNormalize"): k_moments<true> writes the rank's column moments into its part, the caller
+// all-gathers the parts in rank order, and k_norm_merge folds them in that order before k_apply.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -68,10 +71,16 @@ __device__ __forceinline__ void rms_merge(double* mean, double* var, double* cou
     *count = tot;
 }
 
-// blocks 0..D-1: obs column moments (if update_obs); block D: returns update + moments (if step)
+// blocks 0..D-1: obs column moments (if update_obs); block D: returns update + moments (if step).
+// LOCAL (data-parallel, vec_env.py moments_local_ref): thread 0 writes this rank's part of the column,
+// part[2c] = bm and part[2c + 1] = M2 = sum((x - bm)^2), and merges nothing; k_norm_merge folds the
+// ranks' parts.  Otherwise thread 0 merges bv = M2 / n into the running statistics.  The sums are the
+// same instructions in both, so the unsharded statistics keep their bits.
+template <bool LOCAL>
 __global__ __launch_bounds__(NT) void k_moments(const float* __restrict__ obs, int L, int D, const float* __restrict__ reward,
                                                 double* __restrict__ returns, double gamma, double* obs_mean, double* obs_var,
-                                                double* obs_count, double* ret_stats, int update_obs, int step) {
+                                                double* obs_count, double* ret_stats, int update_obs, int step,
+                                                double* __restrict__ part) {
     __shared__ double red[NT];
     const int col = blockIdx.x, t = threadIdx.x;
     const double n = (double)L;
@@ -82,11 +91,14 @@ __global__ __launch_bounds__(NT) void k_moments(const float* __restrict__ obs, i
         const double bm = block_sum(s, red) / n;
         double q = 0.0;
         for (int l = t; l < L; l += NT) { double d = (double)obs[(size_t)l * D + col] - bm; q += d * d; }
-        const double bv = block_sum(q, red) / n;
-        if (t == 0) {
+        const double m2 = block_sum(q, red);
+        if (t != 0) return;
+        if (LOCAL) {
+            part[2 * col] = bm; part[2 * col + 1] = m2;
+        } else {
             double c = *obs_count;   // every column block reads the pre-update count
             double m = obs_mean[col], v = obs_var[col];
-            rms_merge(&m, &v, &c, bm, bv, n);
+            rms_merge(&m, &v, &c, bm, m2 / n, n);
             obs_mean[col] = m; obs_var[col] = v;
         }
     } else {
@@ -100,24 +112,59 @@ __global__ __launch_bounds__(NT) void k_moments(const float* __restrict__ obs, i
         const double bm = block_sum(s, red) / n;
         double q = 0.0;
         for (int l = t; l < L; l += NT) { double d = returns[l] - bm; q += d * d; }
-        const double bv = block_sum(q, red) / n;
-        if (t == 0) rms_merge(&ret_stats[0], &ret_stats[1], &ret_stats[2], bm, bv, n);
+        const double m2 = block_sum(q, red);
+        if (t != 0) return;
+        if (LOCAL) {
+            part[2 * D] = bm; part[2 * D + 1] = m2;
+        } else {
+            rms_merge(&ret_stats[0], &ret_stats[1], &ret_stats[2], bm, m2 / n, n);
+        }
+    }
+}
+
+// Data-parallel statistics (vec_env.py moments_combine_ref): one thread per statistic column folds the
+// R rows of the gathered parts [R][stride] in ascending rank order, every rank with L lanes, and merges
+// the result into the running statistics.  Every rank runs this on the same rows and the same
+// statistics, so the replicas' statistics stay bit-identical.  Plain loads and stores, no atomics; the
+// obs columns all read the pre-update count, which k_apply advances by R * L.
+__global__ __launch_bounds__(NT) void k_norm_merge(const double* __restrict__ parts, int R, size_t stride, int L, int D,
+                                                   double* __restrict__ obs_mean, double* __restrict__ obs_var,
+                                                   const double* __restrict__ obs_count, double* __restrict__ ret_stats,
+                                                   int update_obs, int step) {
+    const int c = blockIdx.x * NT + threadIdx.x;
+    if (c > D || !(c < D ? update_obs : step)) return;
+    const double nb = (double)L;
+    double ma = parts[2 * c], Ma = parts[2 * c + 1], na = nb;
+    for (int r = 1; r < R; ++r) {
+        const double mb = parts[(size_t)r * stride + 2 * c], Mb = parts[(size_t)r * stride + 2 * c + 1];
+        const double nt = na + nb, d = mb - ma;
+        Ma = Ma + Mb + d * d * na * nb / nt;
+        ma = ma + d * nb / nt;
+        na = nt;
+    }
+    const double bv = Ma / na;
+    if (c < D) {
+        double cnt = *obs_count, m = obs_mean[c], v = obs_var[c];
+        rms_merge(&m, &v, &cnt, ma, bv, na);
+        obs_mean[c] = m; obs_var[c] = v;
+    } else {
+        rms_merge(&ret_stats[0], &ret_stats[1], &ret_stats[2], ma, bv, na);
     }
 }
 
 // one thread per obs element (coalesced rows) for obs / terminal obs; threads e < L also do lane
-// e's reward, discounted-return reset and Monitor accumulators; thread 0 advances the obs count
-// (k_moments read the pre-update count)
+// e's reward, discounted-return reset and Monitor accumulators; thread 0 advances the obs count by
+// count_add, the lanes of all ranks (k_moments / k_norm_merge read the pre-update count)
 __global__ __launch_bounds__(NT) void k_apply(const float* __restrict__ obs, const float* __restrict__ term, int L, int D,
                                               const double* __restrict__ obs_mean, const double* __restrict__ obs_var,
-                                              double* __restrict__ obs_count, int count_obs,
+                                              double* __restrict__ obs_count, int count_obs, double count_add,
                                               const double* __restrict__ ret_stats, double clip_obs, double clip_rew, double eps,
                                               const float* __restrict__ reward, const double* __restrict__ reward64,
                                               const uint8_t* __restrict__ done, double* __restrict__ returns, float* __restrict__ obs_out, float* __restrict__ term_out,
                                               float* __restrict__ reward_out, double* __restrict__ ep_ret, int* __restrict__ ep_len,
                                               double* __restrict__ ep_ret_out, int* __restrict__ ep_len_out, int step) {
     const int e = blockIdx.x * NT + threadIdx.x;
-    if (e == 0 && count_obs) *obs_count += (double)L;
+    if (e == 0 && count_obs) *obs_count += count_add;
     if (e < L * D) {
         const int l = e / D, j = e - l * D;
         const double sd = sqrt(obs_var[j] + eps);
@@ -345,6 +392,20 @@ int mrp_norm_set_norm_obs(mrp_norm* n, int norm_obs) {
     return MRP_OK;
 }
 
+// k_apply over this rank's lanes; `lanes_all` is what the obs count advances by (the lanes of all ranks)
+static int norm_apply_launch(mrp_norm* n, const float* obs, const float* reward, const double* reward64, const uint8_t* done,
+                             const float* term, float* obs_out, float* reward_out, float* term_out, double* ep_ret_out,
+                             int* ep_len_out, int step, int upd_obs, double lanes_all) {
+    const int L = n->n_lanes, D = n->obs_dim;
+    const int nthreads = L * D > L ? L * D : L;
+    hipLaunchKernelGGL(k_apply, dim3((nthreads + NT - 1) / NT), dim3(NT), 0, n->stream, obs, term, L, D, n->obs_mean(),
+                       n->obs_var(), n->obs_count(), upd_obs, lanes_all, n->ret_stats(), n->clip_obs, n->clip_rew, n->eps, reward,
+                       reward64, done, n->d_returns, obs_out, term_out, reward_out, n->d_ep_ret, n->d_ep_len, ep_ret_out, ep_len_out,
+                       step);
+    MRP_HIPCHK(n, hipGetLastError());
+    return MRP_OK;
+}
+
 static int norm_launch(mrp_norm* n, const float* obs, const float* reward, const double* reward64, const uint8_t* done,
                        const float* term, float* obs_out, float* reward_out, float* term_out, double* ep_ret_out, int* ep_len_out, int step) {
     MRP_HIPCHK(n, hipSetDevice(n->device));
@@ -352,16 +413,12 @@ static int norm_launch(mrp_norm* n, const float* obs, const float* reward, const
     // SB3 VecNormalize: obs statistics move when training and norm_obs, the returns' when training
     const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
     if (upd_obs || upd_ret) {
-        hipLaunchKernelGGL(k_moments, dim3(D + 1), dim3(NT), 0, n->stream, obs, L, D, reward, n->d_returns, n->gamma,
-                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret);
+        hipLaunchKernelGGL(k_moments<false>, dim3(D + 1), dim3(NT), 0, n->stream, obs, L, D, reward, n->d_returns, n->gamma,
+                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret, nullptr);
         MRP_HIPCHK(n, hipGetLastError());
     }
-    const int nthreads = L * D > L ? L * D : L;
-    hipLaunchKernelGGL(k_apply, dim3((nthreads + NT - 1) / NT), dim3(NT), 0, n->stream, obs, term, L, D, n->obs_mean(),
-                       n->obs_var(), n->obs_count(), upd_obs, n->ret_stats(), n->clip_obs, n->clip_rew, n->eps, reward, reward64,
-                       done, n->d_returns, obs_out, term_out, reward_out, n->d_ep_ret, n->d_ep_len, ep_ret_out, ep_len_out, step);
-    MRP_HIPCHK(n, hipGetLastError());
-    return MRP_OK;
+    return norm_apply_launch(n, obs, reward, reward64, done, term, obs_out, reward_out, term_out, ep_ret_out, ep_len_out, step,
+                             upd_obs, (double)L);
 }
 
 int mrp_norm_reset_device(mrp_norm* n, const float* d_obs, float* d_obs_out) {
@@ -381,6 +438,53 @@ int mrp_norm_step_device(mrp_norm* n, const float* d_obs, const float* d_reward,
                          float* d_obs_out, float* d_reward_out, float* d_term_out, double* d_ep_return, int32_t* d_ep_len) {
     return mrp_norm_step_device_ex(n, d_obs, d_reward, nullptr, d_done, d_term_obs, d_obs_out, d_reward_out, d_term_out,
                                    d_ep_return, d_ep_len);
+}
+
+// ---- data-parallel statistics: local phase, (the caller's all-gather), apply phase --------------------
+int mrp_norm_part_len(int obs_dim) { return obs_dim < 1 ? MRP_E_ARG : 2 * (obs_dim + 1); }
+
+int mrp_norm_local_device(mrp_norm* n, const float* d_obs, const float* d_reward, int step, double* d_part) {
+    if (!n) return norm_bad(n, "mrp_norm_local_device: null handle");
+    if (!d_obs || !d_part || (step && !d_reward)) return norm_bad(n, "mrp_norm_local_device: null pointer");
+    const int L = n->n_lanes, D = n->obs_dim;
+    const size_t f = sizeof(float);
+    if (check_outputs({{d_obs, (size_t)L * D * f}, {step ? d_reward : nullptr, L * f}}, {{d_part, 2 * ((size_t)D + 1) * sizeof(double)}}))
+        return norm_bad(n, "mrp_norm_local_device: d_part overlaps an input");
+    const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
+    if (!upd_obs && !upd_ret) return MRP_OK;   // nothing moves: nothing to exchange
+    MRP_HIPCHK(n, hipSetDevice(n->device));
+    hipLaunchKernelGGL(k_moments<true>, dim3(D + 1), dim3(NT), 0, n->stream, d_obs, L, D, d_reward, n->d_returns, n->gamma,
+                       n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret, d_part);
+    MRP_HIPCHK(n, hipGetLastError());
+    return MRP_OK;
+}
+
+int mrp_norm_apply_device(mrp_norm* n, int R, const double* d_parts, long long part_stride, int step, const float* d_obs,
+                          const float* d_reward, const double* d_reward64, const uint8_t* d_done, const float* d_term_obs,
+                          float* d_obs_out, float* d_reward_out, float* d_term_out, double* d_ep_return, int32_t* d_ep_len) {
+    if (!n) return norm_bad(n, "mrp_norm_apply_device: null handle");
+    if (R < 1) return norm_bad(n, "mrp_norm_apply_device: R < 1");
+    if (!d_parts || !d_obs || !d_obs_out || (step && (!d_reward || !d_done || !d_reward_out)))
+        return norm_bad(n, "mrp_norm_apply_device: null pointer");
+    const int L = n->n_lanes, D = n->obs_dim;
+    if (part_stride < 2 * ((long long)D + 1)) return norm_bad(n, "mrp_norm_apply_device: part_stride < mrp_norm_part_len(obs_dim)");
+    const size_t f = sizeof(float), l = (size_t)L, ld = l * (size_t)D;
+    const Span parts{d_parts, (size_t)R * (size_t)part_stride * sizeof(double)};
+    for (const Span& out : {Span{d_obs_out, ld * f}, Span{d_reward_out, l * f}, Span{d_term_out, ld * f},
+                            Span{d_ep_return, l * sizeof(double)}, Span{d_ep_len, l * sizeof(int32_t)}})
+        if (check_outputs({parts}, {out})) return norm_bad(n, "mrp_norm_apply_device: d_parts overlaps an output");
+    MRP_HIPCHK(n, hipSetDevice(n->device));
+    const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
+    if (upd_obs || upd_ret) {
+        hipLaunchKernelGGL(k_norm_merge, dim3((D + 1 + NT - 1) / NT), dim3(NT), 0, n->stream, d_parts, R, (size_t)part_stride, L, D,
+                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret);
+        MRP_HIPCHK(n, hipGetLastError());
+    }
+    if (!step)   // reset: only the obs pointers are read
+        return norm_apply_launch(n, d_obs, nullptr, nullptr, nullptr, nullptr, d_obs_out, nullptr, nullptr, nullptr, nullptr, 0,
+                                 upd_obs, (double)R * (double)L);
+    return norm_apply_launch(n, d_obs, d_reward, d_reward64, d_done, d_term_obs, d_obs_out, d_reward_out, d_term_out, d_ep_return,
+                             d_ep_len, step ? 1 : 0, upd_obs, (double)R * (double)L);
 }
 
 int mrp_norm_get_stats(mrp_norm* n, double* out) {

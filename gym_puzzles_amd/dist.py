@@ -12,7 +12,8 @@ rank use ``all_gather`` instead (``StepGather(..., to_all=True)``).
 Training with a policy replica and a rollout buffer on every rank needs one more collective, per
 minibatch: ``GradExchange`` all-gathers every rank's flat gradient and statistics into one ``[R, stride]``
 buffer in rank order, which ``DevicePPO`` combines in that fixed order (``ppo.combine_ref``), so every
-replica applies the same bits.
+replica applies the same bits.  ``DeviceVecNormalize(shard=...)`` uses the same exchange with float64 blocks
+(``dtype=torch.float64``), once per ``reset`` / ``step``, for the column moments of its running statistics.
 """
 from __future__ import annotations
 
@@ -97,9 +98,11 @@ class GradExchange:
     """All-gathers one flat float32 block per rank (``DevicePPO``'s gradient before clipping and its five
     statistics) into ``parts`` ``[world, part_stride]``, row ``r`` from rank ``r``; ``part_stride`` is
     ``n_floats`` rounded up to a multiple of 64.  The owner writes its block into ``mine`` ``[part_stride]``
-    and calls the exchange; every rank then holds the same ``parts``."""
+    and calls the exchange; every rank then holds the same ``parts``.  ``dtype=torch.float64`` makes the
+    blocks float64 (``DeviceVecNormalize``'s column moments); the rows arrive bit for bit either way."""
 
-    def __init__(self, shard: Shard, n_floats: int, device, group=None, host_stage: bool = False, force_collective: bool = False):
+    def __init__(self, shard: Shard, n_floats: int, device, group=None, host_stage: bool = False, force_collective: bool = False,
+                 dtype=None):
         """On a device backend the collective is ``all_gather_into_tensor(parts, mine)`` on device tensors,
         asynchronous on the current stream.  ``host_stage``: the collective runs on pinned host buffers (a
         CPU backend such as gloo), with a synchronous device -> host copy before it and a host -> device
@@ -109,12 +112,15 @@ class GradExchange:
         self.shard, self.n_floats, self.group, self.force_collective = shard, int(n_floats), group, force_collective
         if self.n_floats < 1:
             raise ValueError("GradExchange: n_floats must be >= 1")
+        self.dtype = dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"GradExchange: dtype is {dtype}, expected torch.float32 or torch.float64")
         self.world = shard.world
         self.part_stride = -(-self.n_floats // 64) * 64
-        self.mine = torch.zeros(self.part_stride, dtype=torch.float32, device=device)
-        self.parts = torch.zeros((self.world, self.part_stride), dtype=torch.float32, device=device)
-        self.host_mine = torch.zeros(self.part_stride, dtype=torch.float32).pin_memory() if host_stage else None
-        self.host_parts = torch.zeros((self.world, self.part_stride), dtype=torch.float32).pin_memory() if host_stage else None
+        self.mine = torch.zeros(self.part_stride, dtype=dtype, device=device)
+        self.parts = torch.zeros((self.world, self.part_stride), dtype=dtype, device=device)
+        self.host_mine = torch.zeros(self.part_stride, dtype=dtype).pin_memory() if host_stage else None
+        self.host_parts = torch.zeros((self.world, self.part_stride), dtype=dtype).pin_memory() if host_stage else None
 
     def __call__(self):
         """Returns ``parts`` with every rank's ``mine`` in rank order, valid until the next call."""

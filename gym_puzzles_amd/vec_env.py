@@ -252,6 +252,52 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
         return self._b
 
 
+# ---- data-parallel VecNormalize: the rule (numpy float64, every operation rounded on its own, no FMA) ------
+# One set of obs / return statistics over the R * L lanes of R ranks, each with L lanes.  A rank takes the
+# moments of its own lanes (moments_local_ref), the ranks' parts are gathered in rank order, and every rank folds
+# them in that order (moments_combine_ref) and merges the result (rms_merge_ref), so the statistics are the same
+# bits on every rank.  csrc/mrp_norm.hip (k_moments<true>, k_norm_merge) computes the fold and the merge with
+# these operations in this order; its column sums are a 256-thread tree where numpy adds row after row, so the
+# statistics are held to the bound of tests/vecnorm_exact.py, as the unsharded ones are.
+
+def moments_local_ref(x) -> np.ndarray:
+    """One rank's part of the statistic columns ``x`` ``[L]`` or ``[L, C]``: float64 ``[2 C]`` with
+    ``part[2c]`` the column's mean over the L lanes and ``part[2c + 1]`` its ``M2 = sum((x - mean)^2)`` (two
+    float64 passes, M2 not divided by L)."""
+    x = np.asarray(x, np.float64)
+    x = x.reshape(x.shape[0], -1)
+    bm = x.sum(axis=0) / x.shape[0]
+    part = np.empty(2 * x.shape[1], np.float64)
+    part[0::2], part[1::2] = bm, ((x - bm) ** 2).sum(axis=0)
+    return part
+
+
+def moments_combine_ref(parts, L: int):
+    """Fold the ranks' parts ``[R, >= 2 C]`` (row r from rank r, every rank with ``L`` lanes) in ascending rank
+    order: returns ``(bm [C], bv [C], n)``, the batch moments over all ``n = R * L`` lanes.  Chan et al.'s
+    pairwise update, left-associated as written; with one row ``bv`` is ``M2 / L``."""
+    parts = np.asarray(parts, np.float64)
+    ma, Ma, na = parts[0, 0::2].copy(), parts[0, 1::2].copy(), float(L)
+    for r in range(1, parts.shape[0]):
+        mb, Mb, nb = parts[r, 0::2], parts[r, 1::2], float(L)
+        nt = na + nb
+        d = mb - ma
+        Ma = Ma + Mb + d * d * na * nb / nt
+        ma = ma + d * nb / nt
+        na = nt
+    return ma, Ma / na, na
+
+
+def rms_merge_ref(mean, var, count, bm, bv, n):
+    """SB3 ``RunningMeanStd.update_from_moments`` (``rms_merge`` in csrc/mrp_norm.hip): ``(mean, var, count)``
+    after the batch moments ``(bm, bv)`` over ``n`` values."""
+    delta = bm - mean
+    tot = count + n
+    new_mean = mean + delta * n / tot
+    m2 = var * count + bv * n + delta * delta * count * n / tot
+    return new_mean, m2 / tot, tot
+
+
 class DeviceVecNormalize(Handle):
     """stable-baselines3 ``VecNormalize`` + ``Monitor`` statistics kept on the GPU (libmrp's
     ``mrp_norm_*``).  The reference wraps every env in ``Monitor`` and the vector
@@ -266,18 +312,47 @@ class DeviceVecNormalize(Handle):
     the exact value plus what that bound propagates, and exactly ``float32(+-clip)`` where saturated; counts
     and Monitor's returns and lengths are bit-exact; ``term_out``, ``ep_return`` and ``ep_len`` are written
     for done lanes only; NaN propagates as in numpy (a NaN observation makes its column's statistics and
-    outputs NaN from then on, ``+-inf`` saturates)."""
+    outputs NaN from then on, ``+-inf`` saturates).
+
+    Data-parallel (``moments_local_ref`` / ``moments_combine_ref`` / ``rms_merge_ref`` above): with ``shard`` (a
+    ``dist.Shard`` whose ``lanes_per_rank`` is ``n_lanes``) or an explicit ``exchange`` (a float64
+    ``dist.GradExchange`` of at least ``part_len`` values) the statistics are one set over the
+    ``shard.world * n_lanes`` lanes of all ranks, updated as SB3 updates one ``VecNormalize`` over that many envs
+    and bit-identical on every rank; a NaN on any rank poisons its column on every rank.  A ``reset`` / ``step``
+    that moves statistics is then the local phase (``mrp_norm_local_device`` into ``exchange.mine``), the
+    exchange, and the apply phase (``mrp_norm_apply_device``), all on the current torch stream; with
+    ``training`` off nothing is exchanged.  The discounted returns and Monitor stay per lane.  ``group``,
+    ``host_stage`` and ``force_collective`` are ``GradExchange``'s, for the exchange built from ``shard``.  Every
+    rank must hold the same ``(n_lanes, obs_dim, training, norm_obs)``: the first call after construction or after
+    a change of the two flags compares them across ranks (one ``all_gather_object``) and raises ``ValueError`` on
+    every rank on a mismatch, before anything is enqueued.  Use ``sync_from`` after ``set_stats`` on one rank."""
 
     _DESTROY, _LAST_ERROR = "mrp_norm_destroy", "mrp_norm_last_error"
 
     def __init__(self, n_lanes: int, obs_dim: int, device: int = 0, clip_obs: float = 10.0, clip_reward: float = 10.0,
-                 gamma: float = 0.99, epsilon: float = 1e-8):
+                 gamma: float = 0.99, epsilon: float = 1e-8, shard=None, exchange=None, group=None, host_stage: bool = False,
+                 force_collective: bool = False):
         import torch
         self.n_lanes, self.obs_dim, self.device = n_lanes, obs_dim, device
         self._dev = torch.device("cuda", device)
+        if shard is None and exchange is not None:
+            shard = exchange.shard
+        if shard is not None and shard.lanes_per_rank != n_lanes:
+            raise ValueError(f"DeviceVecNormalize: shard.lanes_per_rank is {shard.lanes_per_rank}, n_lanes is {n_lanes}")
         self._open("mrp_norm_create", n_lanes, obs_dim, device, clip_obs, clip_reward, gamma, epsilon)
         self._training = True
         self._norm_obs = True
+        self.shard, self.part_len, self._checked = shard, int(self._L.mrp_norm_part_len(obs_dim)), None
+        if shard is not None and exchange is None:
+            from .dist import GradExchange
+            exchange = GradExchange(shard, self.part_len, self._dev, group=group, host_stage=host_stage,
+                                    force_collective=force_collective, dtype=torch.float64)
+        if exchange is not None:
+            if exchange.dtype != torch.float64 or exchange.n_floats < self.part_len or exchange.world != shard.world:
+                raise ValueError(f"DeviceVecNormalize: the exchange holds {exchange.n_floats} {exchange.dtype} values for "
+                                 f"{exchange.world} ranks, expected at least {self.part_len} torch.float64 for {shard.world}")
+            check_tensor("DeviceVecNormalize", "exchange.mine", exchange.mine, self._dev, torch.float64, (exchange.part_stride,))
+        self.exchange = exchange
 
     def _launch(self, who, tensors, call, *args):
         """Check every given tensor of ``tensors`` (name, tensor, dtype, shape, optional), then launch."""
@@ -286,6 +361,57 @@ class DeviceVecNormalize(Handle):
                 check_tensor(who, name, t, self._dev, dtype, shape)
         self._check_rc(self._L.mrp_norm_set_stream(self._h, stream_of(self._dev)))
         self._check_rc(call(self._h, *args))
+
+    def _launch_dist(self, who, tensors, step, obs, reward, *rest):
+        """The data-parallel form of ``_launch``: local phase, exchange, apply phase when statistics move,
+        else the plain call (no collective); ``rest`` are the arguments of ``mrp_norm_apply_device`` after
+        ``d_reward``."""
+        for name, t, dtype, shape, optional in tensors:
+            if t is not None or not optional:
+                check_tensor(who, name, t, self._dev, dtype, shape)
+        self._check_ranks(who)
+        L, ex = self._L, self.exchange
+        self._check_rc(L.mrp_norm_set_stream(self._h, stream_of(self._dev)))
+        if not (self._training and (self._norm_obs or step)):
+            if step:
+                return self._check_rc(L.mrp_norm_step_device_ex(self._h, obs, reward, *rest))
+            return self._check_rc(L.mrp_norm_reset_device(self._h, obs, rest[3]))
+        self._check_rc(L.mrp_norm_local_device(self._h, obs, reward, step, ex.mine.data_ptr()))
+        parts = ex()
+        self._check_rc(L.mrp_norm_apply_device(self._h, int(parts.shape[0]), parts.data_ptr(), int(parts.shape[1]), step, obs,
+                                               reward, *rest))
+
+    def _check_ranks(self, who):
+        """The ranks must take the same branch, or the collective hangs: one ``all_gather_object`` of
+        ``(n_lanes, obs_dim, training, norm_obs)``, repeated only when the tuple changes."""
+        mine = (int(self.n_lanes), int(self.obs_dim), self._training, self._norm_obs)
+        if mine == self._checked:
+            return
+        ex = self.exchange
+        if ex.world > 1:
+            import torch.distributed as dist
+            seen = [None] * ex.world
+            dist.all_gather_object(seen, mine, group=ex.group)
+            if any(tuple(t) != tuple(seen[0]) for t in seen):
+                raise ValueError(f"{who}: (n_lanes, obs_dim, training, norm_obs) differs across ranks: {seen}")
+        self._checked = mine
+
+    def sync_from(self, src=0, group=None):
+        """Broadcast rank ``src``'s statistics and load them on every rank (after ``set_stats`` / a load on
+        one rank, or on resume; synchronises).  The vector travels on the device under an nccl group and on
+        the host otherwise; ``group`` defaults to the exchange's."""
+        import torch
+        import torch.distributed as dist
+        if group is None and self.exchange is not None:
+            group = self.exchange.group
+        st = np.zeros(2 * self.obs_dim + 4, np.float64)
+        self._check_rc(self._L.mrp_norm_get_stats(self._h, st.ctypes.data))
+        buf = torch.from_numpy(st)
+        if dist.get_backend(group) == "nccl":
+            buf = buf.to(self._dev)
+        dist.broadcast(buf, src, group=group)
+        st = np.ascontiguousarray(buf.cpu().numpy())
+        self._check_rc(self._L.mrp_norm_set_stats(self._h, st.ctypes.data))
 
     @property
     def training(self) -> bool:
@@ -311,6 +437,9 @@ class DeviceVecNormalize(Handle):
         import torch
         shape = (self.n_lanes, self.obs_dim)
         tensors = (("obs", obs, torch.float32, shape, False), ("obs_out", obs_out, torch.float32, shape, False))
+        if self.exchange is not None:
+            return self._launch_dist("DeviceVecNormalize.reset", tensors, 0, ptr(obs), None, None, None, None, ptr(obs_out),
+                                     None, None, None, None)
         self._launch("DeviceVecNormalize.reset", tensors, self._L.mrp_norm_reset_device, ptr(obs), ptr(obs_out))
 
     def step(self, obs, reward, done, obs_out, reward_out, term_obs=None, term_out=None, ep_return=None, ep_len=None,
@@ -326,6 +455,9 @@ class DeviceVecNormalize(Handle):
                    ("term_obs", term_obs, f32, NO, True), ("term_out", term_out, f32, NO, True),
                    ("ep_return", ep_return, f64, N, True), ("ep_len", ep_len, torch.int32, N, True),
                    ("reward64", reward64, f64, N, True))
+        if self.exchange is not None:
+            return self._launch_dist("DeviceVecNormalize.step", tensors, 1, ptr(obs), ptr(reward), ptr(reward64), ptr(done),
+                                     ptr(term_obs), ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
         self._launch("DeviceVecNormalize.step", tensors, self._L.mrp_norm_step_device_ex, ptr(obs), ptr(reward), ptr(reward64),
                      ptr(done), ptr(term_obs), ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
 
@@ -350,7 +482,10 @@ class MultiRobotPuzzleVecNormalize:
     lanes; ``get_original_obs()`` / ``get_original_reward()`` give the raw values."""
 
     def __init__(self, venv: MultiRobotPuzzleVecEnv, training: bool = True, norm_obs: bool = True, norm_reward: bool = True,
-                 clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99, epsilon: float = 1e-8):
+                 clip_obs: float = 10.0, clip_reward: float = 10.0, gamma: float = 0.99, epsilon: float = 1e-8, shard=None,
+                 exchange=None):
+        """``shard`` / ``exchange``: ``DeviceVecNormalize``'s (data-parallel: one set of statistics over the lanes
+        of all ranks, so any rank's ``save()`` writes the one global file)."""
         import torch
         if getattr(venv, "obs_type", "low-dim") != "low-dim":
             raise ValueError("VecNormalize keeps running statistics of low-dim observations; image stacks are used as they are")
@@ -362,7 +497,7 @@ class MultiRobotPuzzleVecNormalize:
         self.num_envs, self.observation_space, self.action_space = venv.num_envs, venv.observation_space, venv.action_space
         N, O = venv.num_envs, venv.observation_space.shape[0]
         dev = torch.device("cuda", venv.device)
-        self.norm = DeviceVecNormalize(N, O, venv.device, clip_obs, clip_reward, gamma, epsilon)
+        self.norm = DeviceVecNormalize(N, O, venv.device, clip_obs, clip_reward, gamma, epsilon, shard=shard, exchange=exchange)
         self.norm.training = training
         self.norm.norm_obs = norm_obs
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
@@ -431,12 +566,12 @@ class MultiRobotPuzzleVecNormalize:
                      epsilon=self.epsilon, training=self.training, norm_obs=self.norm_obs, norm_reward=self.norm_reward)
 
     @classmethod
-    def load(cls, load_path: str, venv: MultiRobotPuzzleVecEnv) -> "MultiRobotPuzzleVecNormalize":
+    def load(cls, load_path: str, venv: MultiRobotPuzzleVecEnv, shard=None, exchange=None) -> "MultiRobotPuzzleVecNormalize":
         with np.load(load_path, allow_pickle=False) as z:
             d = {k: z[k] for k in z.files}
         self = cls(venv, training=bool(d["training"]), norm_obs=bool(d["norm_obs"]), norm_reward=bool(d["norm_reward"]),
                    clip_obs=float(d["clip_obs"]), clip_reward=float(d["clip_reward"]), gamma=float(d["gamma"]),
-                   epsilon=float(d["epsilon"]))
+                   epsilon=float(d["epsilon"]), shard=shard, exchange=exchange)
         self.norm.set_stats({k: d[k] for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")})
         return self
 

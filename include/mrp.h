@@ -269,6 +269,29 @@ int mrp_norm_step_device(mrp_norm* n, const float* d_obs, const float* d_reward,
 int mrp_norm_step_device_ex(mrp_norm* n, const float* d_obs, const float* d_reward, const double* d_reward64,
                             const uint8_t* d_done, const float* d_term_obs, float* d_obs_out, float* d_reward_out,
                             float* d_term_out, double* d_ep_return, int32_t* d_ep_len);
+/* ---- Data-parallel VecNormalize: one set of running statistics over the lanes of all R ranks, each rank with
+ * n_lanes lanes (vec_env.py moments_local_ref / moments_combine_ref; every operation float64 and rounded on
+ * its own).  A reset or step is the local phase, the caller's all-gather of the ranks' parts in rank order,
+ * and the apply phase; every rank then holds the same bits.  Discounted returns and Monitor stay per lane.
+ *   part     float64 [mrp_norm_part_len(obs_dim)] = 2 * (obs_dim + 1): for statistic column c (the obs
+ *            columns, then the discounted returns) part[2c] = the mean over this rank's lanes and
+ *            part[2c + 1] = M2 = sum((x - mean)^2), not divided by n.
+ * mrp_norm_local_device: one launch.  With step != 0 it first advances returns = returns * gamma + reward
+ * (d_reward required) while training.  Only the columns that move are written: the obs columns when training
+ * and norm_obs, the returns column on a step while training; when nothing moves nothing is launched.
+ * mrp_norm_apply_device: d_parts is float64 [R][part_stride], row r from rank r.  One thread per moving
+ * column folds the rows in ascending rank order (na = n_lanes; per row d = mb - ma, nt = na + n_lanes,
+ * Ma = Ma + Mb + d*d*na*n_lanes/nt, ma = ma + d*n_lanes/nt, na = nt) and merges (ma, Ma / na, na) into the
+ * running statistics; then the normalisation of mrp_norm_step_device_ex (step != 0) or mrp_norm_reset_device
+ * (step == 0: only d_obs and d_obs_out are read), with the obs count advanced by R * n_lanes.  With R = 1
+ * the two phases give mrp_norm_step_device_ex's bits.
+ * MRP_E_ARG, before the first HIP call: a null required pointer, R < 1, part_stride < the part length,
+ * d_part overlapping an input, d_parts overlapping an output.  Asynchronous on the context's stream. */
+int mrp_norm_part_len(int obs_dim);   /* MRP_E_ARG for obs_dim < 1 */
+int mrp_norm_local_device(mrp_norm* n, const float* d_obs, const float* d_reward, int step, double* d_part);
+int mrp_norm_apply_device(mrp_norm* n, int R, const double* d_parts, long long part_stride, int step, const float* d_obs,
+                          const float* d_reward, const double* d_reward64, const uint8_t* d_done, const float* d_term_obs,
+                          float* d_obs_out, float* d_reward_out, float* d_term_out, double* d_ep_return, int32_t* d_ep_len);
 /* statistics as float64[2*obs_dim + 4]: obs mean[obs_dim], obs var[obs_dim], obs count,
  * return mean, return var, return count (VecNormalize save/load) */
 int mrp_norm_get_stats(mrp_norm* n, double* out);

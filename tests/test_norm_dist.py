@@ -1,0 +1,237 @@
+"""Data-parallel VecNormalize on the CPU: the rule beside DeviceVecNormalize (gym_puzzles_amd/vec_env.py
+moments_local_ref, moments_combine_ref, rms_merge_ref), driven through tests/vecnorm_dist.py, against the
+exact rule of tests/vecnorm_exact.py over the concatenated R * L lanes, and dist.GradExchange with float64
+blocks on two gloo ranks.
+
+The bounds of vecnorm_exact are used as they are.  A fold adds at most 7 roundings to a statistic's path (4
+on the mean: d, * nb, / nt, +; 7 on the variance: d counted twice, the three products, the division and two
+adds share the square's doubling), so at the smallest shape the path is 9 + 16 + 7 (R - 1) <= 39 roundings
+for R <= 3, inside gamma's 2 * (9 + 16) = 50.  R = 8 at one lane per rank would exceed it a priori and is
+not tested against these bounds.
+"""
+from __future__ import annotations
+
+import os
+import socket
+import sys
+
+import numpy as np
+import pytest
+
+import vecnorm_exact as ve
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (lanes per rank, columns, constructor arguments)
+SHAPES = [(1, 1, "default"), (1, 28, "clipped"), (2, 3, "gamma1"), (63, 5, "default"), (64, 7, "clipped"), (257, 28, "default")]
+STAT_KEYS = ("obs_mean", "obs_var", "ret_mean", "ret_var", "obs_slack", "reward_slack", "term_slack")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _clips(args):
+    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
+
+
+def _dist(R, L, D, **args):
+    from vecnorm_dist import DistVecNormalizeRef
+    return DistVecNormalizeRef(R, L, D, **args)
+
+
+@pytest.mark.parametrize("R", (2, 3))
+@pytest.mark.parametrize("shape", SHAPES, ids=[ve.case_id(s) for s in SHAPES])
+def test_rule_is_within_the_exact_bounds(R, shape):
+    """R ranks of L lanes against one exact VecNormalize over R * L lanes: every statistic below half its
+    bound, outputs within theirs, counts and Monitor bit-exact (vecnorm_exact.judge, unchanged)."""
+    L, D, name = shape
+    args = ve.ARGS[name]
+    inputs = ve.make_inputs(R * L, D, 4000 + 100 * R + SHAPES.index(shape))
+    exact = ve.exact_records(("dist", R, shape), inputs, args, ve.plain_script())
+    got = ve.run_script(ve.RefAdapter(_dist(R, L, D, **args)), inputs, ve.plain_script())
+    w = ve.judge(got, exact, *_clips(args), where=f"R{R}-{ve.case_id(shape)}")
+    print(f"dist rule R={R} {ve.case_id(shape)}, worst error / bound:", {k: float(f"{v:.3g}") for k, v in w.items()})
+    for k in STAT_KEYS:
+        assert w[k] < 0.5, (k, w[k])
+    assert got[-1]["stats"]["obs_count"] == exact[-1]["obs_count"] and got[-1]["stats"]["ret_count"] == exact[-1]["ret_count"]
+
+
+@pytest.mark.parametrize("shape", [(1, 28, "clipped"), (63, 5, "default"), (257, 28, "default")], ids=ve.case_id)
+def test_one_rank_equals_the_restatement_bit_for_bit(shape):
+    """R = 1: the fold is empty and bv = M2 / L, today's rule; every output and statistic equals
+    oracle/vecnorm_ref.py's bits, through an evaluation phase too."""
+    from oracle.vecnorm_ref import VecNormalizeRef
+    L, D, name = shape
+    args = ve.ARGS[name]
+    inputs = ve.make_inputs(L, D, 4100, n_steps=8, with_reward64=True)
+    a = ve.run_script(ve.RefAdapter(VecNormalizeRef(L, D, **args)), inputs, ve.eval_script())
+    b = ve.run_script(ve.RefAdapter(_dist(1, L, D, **args)), inputs, ve.eval_script())
+    for t, (x, y) in enumerate(zip(a, b)):
+        for k, v in x["stats"].items():
+            assert np.array_equal(_bits(v), _bits(y["stats"][k])), f"{k} @{t}"
+        for k in ("obs_out", "reward_out", "term_out", "ep_return", "ep_len"):
+            if x.get(k) is not None:
+                assert np.array_equal(x[k], y[k], equal_nan=True), f"{k} @{t}"
+
+
+def test_combine_ref_is_the_written_fold():
+    """moments_combine_ref against the issue's recurrence written out per column in Python floats (IEEE
+    double, one rounding per operation), and against the moments of the concatenated lanes."""
+    from gym_puzzles_amd.vec_env import moments_combine_ref, moments_local_ref
+    rs = np.random.RandomState(5)
+    L, R, C = 7, 4, 3
+    x = rs.normal(2.0, 3.0, size=(R * L, C))
+    parts = np.stack([moments_local_ref(x[r * L:(r + 1) * L]) for r in range(R)])
+    assert parts.shape == (R, 2 * C) and parts.dtype == np.float64
+    bm, bv, n = moments_combine_ref(parts, L)
+    assert n == R * L
+    for c in range(C):
+        ma, Ma, na = float(parts[0, 2 * c]), float(parts[0, 2 * c + 1]), float(L)
+        for r in range(1, R):
+            mb, Mb, nb = float(parts[r, 2 * c]), float(parts[r, 2 * c + 1]), float(L)
+            nt = na + nb
+            d = mb - ma
+            Ma = Ma + Mb + d * d * na * nb / nt
+            ma = ma + d * nb / nt
+            na = nt
+        assert _bits(bm[c]) == _bits(ma) and _bits(bv[c]) == _bits(Ma / na), c
+    np.testing.assert_allclose(bm, x.mean(axis=0), rtol=1e-13)
+    np.testing.assert_allclose(bv, x.var(axis=0), rtol=1e-12)
+    # one rank: today's bv = q / n, and a 1-d column is one statistic column
+    one = moments_local_ref(x[:L, 0])
+    m1, v1, n1 = moments_combine_ref(one[None], L)
+    assert one.shape == (2,) and n1 == L and _bits(m1[0]) == _bits(one[0]) and _bits(v1[0]) == _bits(one[1] / L)
+    # padded rows (an exchange's stride) are ignored by the caller's slice, and the input is not modified
+    before = parts.copy()
+    moments_combine_ref(parts, L)
+    assert np.array_equal(parts, before)
+
+
+def test_nan_on_one_rank_poisons_its_column_on_every_rank():
+    """Two ranks of 65 lanes, nonfinite_inputs() as rank 1's lanes and clean lanes on rank 0: from the NaN
+    on, column 1's global statistics are NaN (so on every rank), column 2's from the +inf on, the return
+    statistics from the NaN reward on, exactly where numpy's rule over the 130 lanes has them; column 0 stays
+    within the bounds of the exact rule over the 130 lanes."""
+    from oracle.vecnorm_ref import VecNormalizeRef
+    from vecnorm_dist import column0, two_rank_nonfinite_inputs
+    inputs = two_rank_nonfinite_inputs()
+    script = ve.plain_script()
+    got = ve.run_script(ve.RefAdapter(_dist(2, 65, 3)), inputs, script)
+    ref = ve.run_script(ve.RefAdapter(VecNormalizeRef(130, 3)), inputs, script)
+    for t, (g, r) in enumerate(zip(got, ref)):
+        cols = [c for c, first in ((1, 2), (2, 3)) if t >= first]
+        want = np.zeros(3, bool)
+        want[cols] = True
+        assert np.array_equal(np.isnan(g["stats"]["obs_var"]), want), f"obs_var @{t}"
+        assert np.array_equal(np.isnan(g["obs_out"]), np.tile(want, (130, 1))), f"obs_out @{t}: rank 0's lanes included"
+        assert np.isnan(g["stats"]["ret_mean"]) == np.isnan(g["stats"]["ret_var"]) == (t >= 4)
+        for k in ("obs_mean", "obs_var", "ret_mean", "ret_var"):
+            a, b = np.asarray(g["stats"][k]), np.asarray(r["stats"][k])
+            assert np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.isinf(a), np.isinf(b)), f"{k} @{t}"
+        assert g["stats"]["obs_count"] == r["stats"]["obs_count"] and g["stats"]["ret_count"] == r["stats"]["ret_count"]
+    # the unpoisoned column against the exact rule (its rewards are irrelevant to it)
+    exact = ve.exact_records(("dist-nonfinite",), column0(inputs), ve.DEFAULTS, script)
+    for t, (g, e) in enumerate(zip(got, exact)):
+        for k in ("obs_mean", "obs_var"):
+            assert ve.check_stats(g["stats"][k][:1], e["stats"][k], e["stat_bounds"][k], f"{k} @{t}") < 0.5
+        z, prop, tot = e["obs"]
+        ve.check_outputs(np.ascontiguousarray(g["obs_out"][:, :1]), z, tot, 10.0, f"obs_out @{t}", prop=prop)
+
+
+def test_training_off_moves_nothing():
+    """Three training steps, three frozen, two training (eval_script) on 2 x 64 lanes: while frozen the
+    statistics keep their bits and no parts are produced; the whole run is within the exact bounds."""
+    inputs = ve.make_inputs(128, 7, 4200, n_steps=8, with_reward64=True)
+    norm = _dist(2, 64, 7)
+    got = []
+    for op in ve.eval_script():
+        if op == ("training", False):
+            norm.obs_rms.parts = norm.ret_rms.parts = None
+        got += ve.run_script(ve.RefAdapter(norm), inputs, [op])
+        if op[0] == "step" and 3 <= op[1] < 6:
+            assert norm.obs_rms.parts is None and norm.ret_rms.parts is None, "an update ran in evaluation mode"
+    for frozen in got[4:7]:
+        for k, v in got[3]["stats"].items():
+            assert np.array_equal(_bits(v), _bits(frozen["stats"][k])), k
+    assert got[7]["stats"]["ret_count"] == got[3]["stats"]["ret_count"] + 128
+    exact = ve.exact_records(("dist-eval",), inputs, ve.DEFAULTS, ve.eval_script())
+    w = ve.judge(got, exact, where="dist eval")
+    for k in STAT_KEYS:
+        assert w[k] < 0.5, (k, w[k])
+
+
+# ---- dist.GradExchange(dtype=torch.float64) on two gloo ranks ----------------------------------------------
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _payload(rank, n):
+    """float64 bit patterns that arithmetic would not keep: NaN payloads, -0.0, subnormals, the extremes."""
+    special = np.array([0x7FF80000DEADBEEF, 0xFFF0000000000001, 0x8000000000000000, 0x0000000000000001, 0x800FFFFFFFFFFFFF,
+                        0x7FEFFFFFFFFFFFFF, 0x7FF0000000000000, 0x3FF0000000000000], np.uint64)
+    rs = np.random.RandomState(50 + rank)
+    bits = rs.randint(0, 2 ** 63, size=n, dtype=np.int64).astype(np.uint64)
+    bits[:special.size] = special + np.uint64(rank) * np.uint64(2)
+    return bits
+
+
+def _exchange_worker(rank, world, port, n, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch
+    import torch.distributed as dist
+
+    from gym_puzzles_amd.dist import GradExchange, Shard
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        sh = Shard(rank, world, 4)
+        ex = GradExchange(sh, n, device="cpu", dtype=torch.float64)
+        assert ex.mine.dtype == ex.parts.dtype == torch.float64 and ex.part_stride == -(-n // 64) * 64
+        ex.mine[:n].copy_(torch.from_numpy(_payload(rank, n).view(np.float64)))
+        got64 = ex().numpy().view(np.uint64).copy()
+        old = GradExchange(sh, n, device="cpu")            # the default stays float32
+        assert old.mine.dtype == old.parts.dtype == torch.float32 and old.dtype == torch.float32
+        old.mine[:n].copy_(torch.from_numpy(_payload(rank, n).astype(np.uint32).view(np.float32)))
+        got32 = old().numpy().view(np.uint32).copy()
+        q.put((rank, got64, got32))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_exchange_carries_float64_rows_bit_for_bit():
+    """Two gloo ranks: every rank's ``parts`` holds both senders' float64 rows with their bit patterns (NaN
+    payloads, -0.0, subnormals), in rank order; the float32 default does the same with float32 blocks."""
+    import torch
+    import torch.multiprocessing as mp
+
+    from gym_puzzles_amd.dist import GradExchange, Shard
+    world, n = 2, 58                  # the part length of 28 obs columns: one stride of 64 with padding
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_exchange_worker, args=(r, world, port, n, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    results = [q.get(timeout=240) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(r[0] for r in results) == [0, 1]
+    for rank, got64, got32 in results:
+        assert got64.shape == got32.shape == (2, 64)
+        for r in range(world):
+            assert np.array_equal(got64[r, :n], _payload(r, n)), f"rank {rank}: float64 row {r}"
+            assert np.array_equal(got32[r, :n], _payload(r, n).astype(np.uint32)), f"rank {rank}: float32 row {r}"
+            assert not got64[r, n:].any() and not got32[r, n:].any()
+    with pytest.raises(ValueError):
+        GradExchange(Shard(0, 1, 4), n, device="cpu", dtype=torch.int32)
+    one = GradExchange(Shard(0, 1, 4), n, device="cpu", dtype=torch.float64)       # world size 1: the copy
+    one.mine[:n].copy_(torch.from_numpy(_payload(0, n).view(np.float64)))
+    assert np.array_equal(one().numpy().view(np.uint64)[0, :n], _payload(0, n))
