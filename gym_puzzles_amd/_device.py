@@ -28,6 +28,14 @@ def check_tensor(who, name, t, dev, dtype, shape):
         raise ValueError(f"{who}: {name} is not contiguous")
 
 
+def check_tensors(who, dev, specs):
+    """``check_tensor`` on every ``(name, tensor, dtype, shape, optional)`` of ``specs``, in order; None
+    passes only where ``optional``."""
+    for name, t, dtype, shape, optional in specs:
+        if t is not None or not optional:
+            check_tensor(who, name, t, dev, dtype, shape)
+
+
 def ptr(t):
     """The device address of a checked tensor as a pointer argument of the ABI (a plain int: the ABI's
     ``argtypes`` convert it); None (NULL) for None."""

@@ -392,6 +392,10 @@ int mrp_norm_set_norm_obs(mrp_norm* n, int norm_obs) {
     return MRP_OK;
 }
 
+// SB3 VecNormalize: obs statistics move when training and norm_obs, the returns' when training (and not in a reset)
+struct Moves { int obs, ret; };
+static Moves norm_moves(const mrp_norm* n, int step) { return Moves{n->training && n->norm_obs, step && n->training}; }
+
 // k_apply over this rank's lanes; `lanes_all` is what the obs count advances by (the lanes of all ranks)
 static int norm_apply_launch(mrp_norm* n, const float* obs, const float* reward, const double* reward64, const uint8_t* done,
                              const float* term, float* obs_out, float* reward_out, float* term_out, double* ep_ret_out,
@@ -410,15 +414,14 @@ static int norm_launch(mrp_norm* n, const float* obs, const float* reward, const
                        const float* term, float* obs_out, float* reward_out, float* term_out, double* ep_ret_out, int* ep_len_out, int step) {
     MRP_HIPCHK(n, hipSetDevice(n->device));
     const int L = n->n_lanes, D = n->obs_dim;
-    // SB3 VecNormalize: obs statistics move when training and norm_obs, the returns' when training
-    const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
-    if (upd_obs || upd_ret) {
+    const Moves upd = norm_moves(n, step);
+    if (upd.obs || upd.ret) {
         hipLaunchKernelGGL(k_moments<false>, dim3(D + 1), dim3(NT), 0, n->stream, obs, L, D, reward, n->d_returns, n->gamma,
-                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret, nullptr);
+                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd.obs, upd.ret, nullptr);
         MRP_HIPCHK(n, hipGetLastError());
     }
     return norm_apply_launch(n, obs, reward, reward64, done, term, obs_out, reward_out, term_out, ep_ret_out, ep_len_out, step,
-                             upd_obs, (double)L);
+                             upd.obs, (double)L);
 }
 
 int mrp_norm_reset_device(mrp_norm* n, const float* d_obs, float* d_obs_out) {
@@ -450,11 +453,11 @@ int mrp_norm_local_device(mrp_norm* n, const float* d_obs, const float* d_reward
     const size_t f = sizeof(float);
     if (check_outputs({{d_obs, (size_t)L * D * f}, {step ? d_reward : nullptr, L * f}}, {{d_part, 2 * ((size_t)D + 1) * sizeof(double)}}))
         return norm_bad(n, "mrp_norm_local_device: d_part overlaps an input");
-    const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
-    if (!upd_obs && !upd_ret) return MRP_OK;   // nothing moves: nothing to exchange
+    const Moves upd = norm_moves(n, step);
+    if (!upd.obs && !upd.ret) return MRP_OK;   // nothing moves: nothing to exchange
     MRP_HIPCHK(n, hipSetDevice(n->device));
     hipLaunchKernelGGL(k_moments<true>, dim3(D + 1), dim3(NT), 0, n->stream, d_obs, L, D, d_reward, n->d_returns, n->gamma,
-                       n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret, d_part);
+                       n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd.obs, upd.ret, d_part);
     MRP_HIPCHK(n, hipGetLastError());
     return MRP_OK;
 }
@@ -474,17 +477,15 @@ int mrp_norm_apply_device(mrp_norm* n, int R, const double* d_parts, long long p
                             Span{d_ep_return, l * sizeof(double)}, Span{d_ep_len, l * sizeof(int32_t)}})
         if (check_outputs({parts}, {out})) return norm_bad(n, "mrp_norm_apply_device: d_parts overlaps an output");
     MRP_HIPCHK(n, hipSetDevice(n->device));
-    const int upd_obs = n->training && n->norm_obs, upd_ret = step && n->training;
-    if (upd_obs || upd_ret) {
+    const Moves upd = norm_moves(n, step);
+    if (upd.obs || upd.ret) {
         hipLaunchKernelGGL(k_norm_merge, dim3((D + 1 + NT - 1) / NT), dim3(NT), 0, n->stream, d_parts, R, (size_t)part_stride, L, D,
-                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd_obs, upd_ret);
+                           n->obs_mean(), n->obs_var(), n->obs_count(), n->ret_stats(), upd.obs, upd.ret);
         MRP_HIPCHK(n, hipGetLastError());
     }
-    if (!step)   // reset: only the obs pointers are read
-        return norm_apply_launch(n, d_obs, nullptr, nullptr, nullptr, nullptr, d_obs_out, nullptr, nullptr, nullptr, nullptr, 0,
-                                 upd_obs, (double)R * (double)L);
+    // in a reset (step == 0) k_apply reads only the obs pointers
     return norm_apply_launch(n, d_obs, d_reward, d_reward64, d_done, d_term_obs, d_obs_out, d_reward_out, d_term_out, d_ep_return,
-                             d_ep_len, step ? 1 : 0, upd_obs, (double)R * (double)L);
+                             d_ep_len, step != 0, upd.obs, (double)R * (double)L);
 }
 
 int mrp_norm_get_stats(mrp_norm* n, double* out) {

@@ -579,46 +579,28 @@ struct mrp_ppo {
 
 namespace {
 
-// gradients and statistics of one minibatch into `d_grad` (the object's own vector when null) and d_stats.
-// old_v: clip_range_vf's old values (cv), null for none.  words: the progress words of a predicated call
-// (null: none); kl_limit >= 0 lets k_ppo_norm set `stopped`.
-int ppo_grad_launch(mrp_ppo* o, const char* who, hipStream_t st, int B, const float* obs, const float* actions, const float* old_lp,
-                    const float* adv, const float* ret, float clip, float ent_coef, double vf_coef, double max_norm, float* d_grad,
-                    float* d_stats, const float* old_v = nullptr, float cv = -1.0f, int* words = nullptr, double kl_limit = -1.0) {
-    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
-    if (B < 1) return bad("B < 1");
-    if (B > o->max_batch) return bad("B > max_batch");
-    if (!obs || !actions || !old_lp || !adv || !ret || !d_stats) return bad("null pointer");
-    const size_t f = sizeof(float), nB = (size_t)B * f;   // d_grad is null in a step: the object's own vector
-    if (const char* what = check_outputs(
-            {{obs, nB * o->pn.net.obs_dim}, {actions, nB * o->pn.net.act_dim}, {old_lp, nB}, {adv, nB}, {ret, nB}},
-            {{d_stats, NSTAT * f}, {d_grad, (size_t)o->n_params * f}}))
-        return bad(what);
-    mrp_policy* p = o->policy;
-    if (!p->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
-    MRP_HIPCHK(o, hipSetDevice(o->device));
-    const int P = o->n_params, pb = (P + P_NT - 1) / P_NT;
-    if (o->seen_version != p->version) {
-        hipLaunchKernelGGL(k_ppo_import, dim3(pb), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P, o->param(), o->d_rows);
-        o->seen_version = p->version;
-    }
-    const int n_chunks = (B + CHUNK - 1) / CHUNK;
-    hipLaunchKernelGGL(k_ppo_fb, dim3((B + P_TILE - 1) / P_TILE), dim3(P_NT), 0, st, o->pn, B, obs, actions, old_lp, adv, ret, clip,
-                       (float)(2.0 * vf_coef), (float)(1.0 / (double)B), old_v, cv, words);
-    const int waves = o->n_tiles * n_chunks;
-    hipLaunchKernelGGL(k_ppo_wgrad, dim3((waves + 3) / 4), dim3(P_NT), 0, st, o->d_tiles, o->n_tiles, B, obs, o->pn.net.obs_dim,
-                       o->d_partial, P, words);
-    hipLaunchKernelGGL(k_ppo_bsum, dim3(n_chunks, (o->n_elems + P_NT - 1) / P_NT + 1), dim3(P_NT), 0, st, o->d_elems, o->n_elems, B,
-                       o->pn.sterm, o->d_partial, P, o->d_spart, words);
-    float* g = d_grad ? d_grad : o->grad();
-    hipLaunchKernelGGL(k_ppo_reduce, dim3(pb), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, o->pn.net.act_dim, ent_coef, g, words);
-    hipLaunchKernelGGL(k_ppo_norm<false>, dim3(1), dim3(P_NT), 0, st, g, P, max_norm, o->d_spart, n_chunks, B, o->coef(), d_stats, words,
-                       kl_limit);
-    MRP_HIPCHK(o, hipGetLastError());
-    return MRP_OK;
+// the one way an entry refuses a call: "<who>: <what>" where its last_error reads it
+int fail(std::string& err, const char* who, const char* what, int rc = MRP_E_ARG) {
+    err = std::string(who) + ": " + what;
+    return rc;
 }
 
-// clip + Adam on the object's own gradient; `words` as in ppo_grad_launch
+const char* const NO_PARAMS = "no parameters yet (mrp_policy_set_params)";   // with MRP_E_STATE
+// the ABI's seven Adam scalars, which carry these names in every entry that takes them
+#define ADAM_K (AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps})
+
+// the master copy and the row-major image follow the policy's parameters when those were set since the last call
+void import_if_stale(mrp_ppo* o, hipStream_t st) {
+    const mrp_policy* p = o->policy;
+    if (o->seen_version != p->version) {
+        const int P = o->n_params;
+        hipLaunchKernelGGL(k_ppo_import, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P,
+                           o->param(), o->d_rows);
+        o->seen_version = p->version;
+    }
+}
+
+// clip + Adam on the object's own gradient; `words`: the progress words of a predicated call (null: none)
 int ppo_adam_launch(mrp_ppo* o, hipStream_t st, AdamK k, int* words) {
     const int P = o->n_params;
     mrp_policy* p = o->policy;
@@ -626,6 +608,66 @@ int ppo_adam_launch(mrp_ppo* o, hipStream_t st, AdamK k, int* words) {
                        o->m(), o->v(), o->d_idx, o->d_idx + P, p->d_params, o->d_rows, const_cast<float*>(p->net.std), k, words);
     MRP_HIPCHK(o, hipGetLastError());
     return MRP_OK;
+}
+
+// One minibatch, as every entry hands it over.  `in`: the caller's six arrays (old_v is read under cv >= 0); with `index`
+// the minibatch is rows index[0..B) of their n_rows rows, gathered into the stage, where `normalize` takes the advantages
+// too.  `words`: the progress words of a predicated call (null: none).  With `d_grad` the gradient alone: no clip, no
+// Adam, no stop; else the step, with `adam` and the stop above 1.5 * target_kl (negative: none).
+struct Minibatch {
+    const char* who; hipStream_t st; int B; Fields in; float clip, ent_coef; double vf_coef; float* d_stats;   // every entry's
+    const long long* index = nullptr; long long n_rows = 0; bool normalize = false; float cv = -1.0f; int* words = nullptr;
+    double target_kl = -1.0, max_norm = 1.0; float* d_grad = nullptr; AdamK adam = {};
+};
+
+int ppo_minibatch(mrp_ppo* o, Minibatch a) {
+    const int B = a.B;
+    if (B < 1) return fail(o->err, a.who, "B < 1");
+    if (B > o->max_batch) return fail(o->err, a.who, "B > max_batch");
+    if (!a.in.obs || !a.in.act || !a.in.old_lp || !a.in.adv || !a.in.ret || !a.d_stats) return fail(o->err, a.who, "null pointer");
+    if (!(a.cv < 0.0f) && !a.in.old_v) return fail(o->err, a.who, "clip_range_vf is set and d_old_values is null");
+    if (a.index && a.n_rows < 1) return fail(o->err, a.who, "n_rows < 1");
+    if (a.cv < 0.0f) a.in.old_v = nullptr;
+    const Net& net = o->pn.net;
+    const size_t f = sizeof(float), rows = a.index ? (size_t)a.n_rows : (size_t)B;
+    if (const char* what = check_outputs({{a.index, (size_t)B * sizeof(long long)}, {a.in.obs, rows * net.obs_dim * f},
+                                          {a.in.act, rows * net.act_dim * f}, {a.in.old_v, rows * f}, {a.in.old_lp, rows * f},
+                                          {a.in.adv, rows * f}, {a.in.ret, rows * f}},
+                                         {{a.d_stats, NSTAT * f}, {a.d_grad, (size_t)o->n_params * f}}))
+        return fail(o->err, a.who, what);
+    if (!o->policy->ready) return fail(o->err, a.who, NO_PARAMS, MRP_E_STATE);
+    MRP_HIPCHK(o, hipSetDevice(o->device));
+    const hipStream_t st = a.st;
+    const int P = o->n_params, n_chunks = (B + CHUNK - 1) / CHUNK;
+    Fields in = a.in;
+    const bool norm = a.normalize && B > 1;      // SB3 skips a minibatch of one sample
+    if (a.index || norm) {
+        const Stage sg = o->stage();
+        const int first = B < CHUNK ? B : CHUNK;
+        hipLaunchKernelGGL(k_ppo_gather, dim3(n_chunks, (first + G_ROWS - 1) / G_ROWS), dim3(P_NT), 0, st, a.words, a.words, B, a.index,
+                           (long long)rows, in, sg, net.obs_dim, net.act_dim, norm ? 1 : 0, o->d_advpart);
+        if (norm) {
+            double* sq = o->d_advpart + o->max_chunks;
+            hipLaunchKernelGGL(k_ppo_advnorm<0>, dim3(n_chunks), dim3(P_NT), 0, st, a.words, B, n_chunks, sg.adv, o->d_advpart, sq);
+            hipLaunchKernelGGL(k_ppo_advnorm<1>, dim3(n_chunks), dim3(P_NT), 0, st, a.words, B, n_chunks, sg.adv, o->d_advpart, sq);
+        }
+        in = Fields{sg.obs, sg.act, in.old_v ? sg.old_v : nullptr, sg.old_lp, sg.adv, sg.ret};
+    }
+    import_if_stale(o, st);
+    float* g = a.d_grad ? a.d_grad : o->grad();
+    hipLaunchKernelGGL(k_ppo_fb, dim3((B + P_TILE - 1) / P_TILE), dim3(P_NT), 0, st, o->pn, B, in.obs, in.act, in.old_lp, in.adv, in.ret,
+                       a.clip, (float)(2.0 * a.vf_coef), (float)(1.0 / (double)B), in.old_v, a.cv, a.words);
+    const int waves = o->n_tiles * n_chunks;
+    hipLaunchKernelGGL(k_ppo_wgrad, dim3((waves + 3) / 4), dim3(P_NT), 0, st, o->d_tiles, o->n_tiles, B, in.obs, net.obs_dim,
+                       o->d_partial, P, a.words);
+    hipLaunchKernelGGL(k_ppo_bsum, dim3(n_chunks, (o->n_elems + P_NT - 1) / P_NT + 1), dim3(P_NT), 0, st, o->d_elems, o->n_elems, B,
+                       o->pn.sterm, o->d_partial, P, o->d_spart, a.words);
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((P + P_NT - 1) / P_NT), dim3(P_NT), 0, st, o->d_partial, P, n_chunks, net.act_dim, a.ent_coef,
+                       g, a.words);
+    hipLaunchKernelGGL(k_ppo_norm<false>, dim3(1), dim3(P_NT), 0, st, g, P, a.d_grad ? 1.0 : a.max_norm, o->d_spart, n_chunks, B,
+                       o->coef(), a.d_stats, a.words, a.d_grad || a.target_kl < 0.0 ? -1.0 : 1.5 * a.target_kl);
+    MRP_HIPCHK(o, hipGetLastError());
+    return a.d_grad ? MRP_OK : ppo_adam_launch(o, st, a.adam, a.words);
 }
 
 }  // namespace
@@ -650,13 +692,13 @@ void mrp_ppo_destroy(mrp_ppo* o) {
 int mrp_ppo_create(mrp_policy* policy, int max_batch, mrp_ppo** out) {
     std::string& err = g_ppo_create_error;
     err.clear();
-    auto bad = [&](const char* what) { err = std::string("mrp_ppo_create: ") + what; return MRP_E_ARG; };
-    if (!out) return bad("null out");
+    const char* who = "mrp_ppo_create";
+    if (!out) return fail(err, who, "null out");
     *out = nullptr;
-    if (!policy) return bad("null policy");
-    if (max_batch < 1 || max_batch > (1 << 20)) return bad("max_batch outside 1..1048576");
+    if (!policy) return fail(err, who, "null policy");
+    if (max_batch < 1 || max_batch > (1 << 20)) return fail(err, who, "max_batch outside 1..1048576");
     mrp_ppo* o = new (std::nothrow) mrp_ppo();
-    if (!o) return bad("out of host memory");
+    if (!o) return fail(err, who, "out of host memory");
     o->policy = policy; o->device = policy->device; o->max_batch = max_batch;
     o->max_chunks = (max_batch + CHUNK - 1) / CHUNK;
     const Net& net = policy->net;
@@ -760,9 +802,11 @@ int mrp_ppo_grad_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs,
                         const float* d_advantages, const float* d_returns, float clip_range, float ent_coef, double vf_coef,
                         float* d_grad, float* d_stats) {
     if (!o) return MRP_E_ARG;
-    if (!d_grad) { o->err = "mrp_ppo_grad_device: null pointer"; return MRP_E_ARG; }
-    return ppo_grad_launch(o, "mrp_ppo_grad_device", (hipStream_t)hip_stream, B, d_obs, d_actions, d_old_log_probs, d_advantages,
-                           d_returns, clip_range, ent_coef, vf_coef, 1.0, d_grad, d_stats);
+    if (!d_grad) return fail(o->err, "mrp_ppo_grad_device", "null pointer");
+    Minibatch a{"mrp_ppo_grad_device", (hipStream_t)hip_stream, B, {d_obs, d_actions, nullptr, d_old_log_probs, d_advantages, d_returns},
+                clip_range, ent_coef, vf_coef, d_stats};
+    a.d_grad = d_grad;
+    return ppo_minibatch(o, a);
 }
 
 int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs, const float* d_actions, const float* d_old_log_probs,
@@ -770,11 +814,10 @@ int mrp_ppo_step_device(mrp_ppo* o, void* hip_stream, int B, const float* d_obs,
                         double max_grad_norm, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
                         float step_size, float eps, float* d_stats) {
     if (!o) return MRP_E_ARG;
-    const int rc = ppo_grad_launch(o, "mrp_ppo_step_device", (hipStream_t)hip_stream, B, d_obs, d_actions, d_old_log_probs,
-                                   d_advantages, d_returns, clip_range, ent_coef, vf_coef, max_grad_norm, nullptr, d_stats);
-    if (rc != MRP_OK) return rc;
-    return ppo_adam_launch(o, (hipStream_t)hip_stream, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps},
-                           nullptr);
+    Minibatch a{"mrp_ppo_step_device", (hipStream_t)hip_stream, B, {d_obs, d_actions, nullptr, d_old_log_probs, d_advantages, d_returns},
+                clip_range, ent_coef, vf_coef, d_stats};
+    a.max_norm = max_grad_norm; a.adam = ADAM_K;
+    return ppo_minibatch(o, a);
 }
 
 int mrp_ppo_begin_device(mrp_ppo* o, void* hip_stream) {
@@ -791,44 +834,11 @@ int mrp_ppo_minibatch_device(mrp_ppo* o, void* hip_stream, int B, const long lon
                              float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
                              float step_size, float eps, float* d_grad, float* d_stats) {
     if (!o) return MRP_E_ARG;
-    const char* who = "mrp_ppo_minibatch_device";
-    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
-    if (B < 1) return bad("B < 1");
-    if (B > o->max_batch) return bad("B > max_batch");
-    if (!d_obs || !d_actions || !d_old_log_probs || !d_advantages || !d_returns || !d_stats) return bad("null pointer");
-    if (!(clip_range_vf < 0.0f) && !d_old_values) return bad("clip_range_vf is set and d_old_values is null");
-    if (d_index && n_rows < 1) return bad("n_rows < 1");
-    if (clip_range_vf < 0.0f) d_old_values = nullptr;
-    const Net& net = o->pn.net;
-    const size_t f = sizeof(float), rows = d_index ? (size_t)n_rows : (size_t)B;
-    if (const char* what = check_outputs({{d_index, (size_t)B * sizeof(long long)}, {d_obs, rows * net.obs_dim * f},
-                                          {d_actions, rows * net.act_dim * f}, {d_old_values, rows * f}, {d_old_log_probs, rows * f},
-                                          {d_advantages, rows * f}, {d_returns, rows * f}},
-                                         {{d_stats, NSTAT * f}, {d_grad, (size_t)o->n_params * f}}))
-        return bad(what);
-    if (!o->policy->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
-    MRP_HIPCHK(o, hipSetDevice(o->device));
-    const hipStream_t st = (hipStream_t)hip_stream;
-    Fields in{d_obs, d_actions, d_old_values, d_old_log_probs, d_advantages, d_returns};
-    const bool norm = normalize_advantage && B > 1;      // SB3 skips a minibatch of one sample
-    if (d_index || norm) {
-        const Stage sg = o->stage();
-        const int n_chunks = (B + CHUNK - 1) / CHUNK, first = B < CHUNK ? B : CHUNK;
-        hipLaunchKernelGGL(k_ppo_gather, dim3(n_chunks, (first + G_ROWS - 1) / G_ROWS), dim3(P_NT), 0, st, o->d_words, o->d_words, B,
-                           d_index, (long long)rows, in, sg, net.obs_dim, net.act_dim, norm ? 1 : 0, o->d_advpart);
-        if (norm) {
-            double* sq = o->d_advpart + o->max_chunks;
-            hipLaunchKernelGGL(k_ppo_advnorm<0>, dim3(n_chunks), dim3(P_NT), 0, st, o->d_words, B, n_chunks, sg.adv, o->d_advpart, sq);
-            hipLaunchKernelGGL(k_ppo_advnorm<1>, dim3(n_chunks), dim3(P_NT), 0, st, o->d_words, B, n_chunks, sg.adv, o->d_advpart, sq);
-        }
-        in = Fields{sg.obs, sg.act, d_old_values ? sg.old_v : nullptr, sg.old_lp, sg.adv, sg.ret};
-    }
-    // the gradient alone (d_grad): no clip, no Adam, no stop
-    const int rc = ppo_grad_launch(o, who, st, B, in.obs, in.act, in.old_lp, in.adv, in.ret, clip_range, ent_coef, vf_coef,
-                                   d_grad ? 1.0 : max_grad_norm, d_grad, d_stats, in.old_v, clip_range_vf, o->d_words,
-                                   d_grad || target_kl < 0.0 ? -1.0 : 1.5 * target_kl);
-    if (rc != MRP_OK || d_grad) return rc;
-    return ppo_adam_launch(o, st, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps}, o->d_words);
+    Minibatch a{"mrp_ppo_minibatch_device", (hipStream_t)hip_stream, B,
+                {d_obs, d_actions, d_old_values, d_old_log_probs, d_advantages, d_returns}, clip_range, ent_coef, vf_coef, d_stats};
+    a.index = d_index; a.n_rows = n_rows; a.normalize = normalize_advantage != 0; a.cv = clip_range_vf;
+    a.words = o->d_words; a.target_kl = target_kl; a.max_norm = max_grad_norm; a.d_grad = d_grad; a.adam = ADAM_K;
+    return ppo_minibatch(o, a);
 }
 
 int mrp_ppo_apply_device(mrp_ppo* o, void* hip_stream, int R, const float* d_parts, long long part_stride, double target_kl,
@@ -836,27 +846,21 @@ int mrp_ppo_apply_device(mrp_ppo* o, void* hip_stream, int R, const float* d_par
                          float step_size, float eps, float* d_stats) {
     if (!o) return MRP_E_ARG;
     const char* who = "mrp_ppo_apply_device";
-    auto bad = [&](const char* what) { o->err = std::string(who) + ": " + what; return MRP_E_ARG; };
-    if (R < 1 || R > 64) return bad("R outside 1..64");
-    if (!d_parts || !d_stats) return bad("null pointer");
+    if (R < 1 || R > 64) return fail(o->err, who, "R outside 1..64");
+    if (!d_parts || !d_stats) return fail(o->err, who, "null pointer");
     const int P = o->n_params;
-    if (part_stride < (long long)P + NSTAT) return bad("part_stride < n_params + 5");
+    if (part_stride < (long long)P + NSTAT) return fail(o->err, who, "part_stride < n_params + 5");
     const size_t f = sizeof(float);
-    if (const char* what = check_outputs({{d_parts, (size_t)R * (size_t)part_stride * f}}, {{d_stats, NSTAT * f}})) return bad(what);
-    mrp_policy* p = o->policy;
-    if (!p->ready) { o->err = std::string(who) + ": no parameters yet (mrp_policy_set_params)"; return MRP_E_STATE; }
+    if (const char* what = check_outputs({{d_parts, (size_t)R * (size_t)part_stride * f}}, {{d_stats, NSTAT * f}})) return fail(o->err, who, what);
+    if (!o->policy->ready) return fail(o->err, who, NO_PARAMS, MRP_E_STATE);
     MRP_HIPCHK(o, hipSetDevice(o->device));
     const hipStream_t st = (hipStream_t)hip_stream;
-    const int pb = (P + P_NT - 1) / P_NT;
-    if (o->seen_version != p->version) {
-        hipLaunchKernelGGL(k_ppo_import, dim3(pb), dim3(P_NT), 0, st, P, p->d_params, o->d_idx, o->d_idx + P, o->param(), o->d_rows);
-        o->seen_version = p->version;
-    }
+    import_if_stale(o, st);
     hipLaunchKernelGGL(k_ppo_combine, dim3((P + NSTAT + P_NT - 1) / P_NT), dim3(P_NT), 0, st, d_parts, R, (size_t)part_stride, P,
                        (float)(1.0 / (double)R), o->grad(), d_stats, o->coef() + 1, o->d_words);
     hipLaunchKernelGGL(k_ppo_norm<true>, dim3(1), dim3(P_NT), 0, st, o->grad(), P, max_grad_norm, nullptr, 0, 0, o->coef(), nullptr,
                        o->d_words, target_kl < 0.0 ? -1.0 : 1.5 * target_kl);
-    return ppo_adam_launch(o, st, AdamK{beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, step_size, eps}, o->d_words);
+    return ppo_adam_launch(o, st, ADAM_K, o->d_words);
 }
 
 int mrp_ppo_progress(mrp_ppo* o, void* hip_stream, int* stopped, int* applied) {

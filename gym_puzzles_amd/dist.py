@@ -43,6 +43,31 @@ def shard_from_env(lanes_per_rank: int) -> Shard:
     return Shard(int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), lanes_per_rank)
 
 
+def agree(who, what, value, world, group=None):
+    """``ValueError`` on every rank unless all ``world`` ranks hold the same ``value`` (a tuple named by ``what``), so
+    that they go on to enqueue the same collectives: one gather of the values when ``world > 1``, else no collective."""
+    if world > 1:
+        import torch.distributed as dist
+        seen = [None] * world
+        dist.all_gather_object(seen, value, group=group)
+        if any(tuple(v) != tuple(seen[0]) for v in seen):
+            raise ValueError(f"{who}: {what} differs across ranks: {seen}")
+
+
+def broadcast_array(array, src, group, device):
+    """Rank ``src``'s numpy ``array`` on every rank, bit for bit, as a new array of the same dtype and shape
+    (every rank passes one of that dtype and shape).  It travels on ``device`` under an nccl group and on the
+    host otherwise."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    buf = torch.from_numpy(np.array(array))      # a contiguous copy: the caller's array is not written
+    if dist.get_backend(group) == "nccl":
+        buf = buf.to(device)
+    dist.broadcast(buf, src, group=group)
+    return buf.cpu().numpy()
+
+
 class StepGather:
     """Packs one step's outputs of this rank and gathers every rank's block to rank 0."""
 

@@ -73,7 +73,8 @@ import math
 
 import numpy as np
 
-from ._device import Handle, check_tensor, ptr, stream_of
+from ._device import Handle, check_tensor, check_tensors, ptr, stream_of
+from .dist import agree, broadcast_array
 from .policy import (_INV_LN2, _LN2_HI, _LN2_LO, _TANH_C, LOG_SQRT_2PI, PolicyParams, _activate, _layers,  # noqa: F401
                      flatten_params, fma32, linear_ref, state_dict_from_params, unflatten_params)
 
@@ -436,6 +437,10 @@ def ppo_train_dist_ref(params, state, datas, epochs, batch_size, perms, *, old_v
 
 
 # ---- the device class --------------------------------------------------------------------------------
+def _or_off(x):        # an optional option as the ABI takes it: negative is off
+    return -1.0 if x is None else x
+
+
 class DevicePPO(Handle):
     """The rule on the device: ``grad`` is ``ppo_grad_ref``, ``step`` is ``ppo_step_ref`` written into
     ``policy``'s device parameters in place (the next ``policy.act`` uses them), ``train`` is SB3's
@@ -548,15 +553,14 @@ class DevicePPO(Handle):
             raise ValueError("DevicePPO: the minibatch holds no sample")
         if self.clip_range_vf is not None and old_values is None:
             raise ValueError("DevicePPO: clip_range_vf is set and old_values is missing")
-        named = (("obs", obs, (rows, self.policy.obs_dim)), ("actions", actions, (rows, self.policy.act_dim)),
-                 ("old_values", old_values, (rows,)), ("old_log_probs", old_log_probs, (rows,)), ("advantages", advantages, (rows,)),
-                 ("returns", returns, (rows,)))
-        for name, t, shape in named:
-            if t is not None:
-                check_tensor("DevicePPO", name, t, self.device, f32, shape)
+        # a missing field passes here and is the library's "null pointer"
+        named = (("obs", obs, f32, (rows, self.policy.obs_dim), True), ("actions", actions, f32, (rows, self.policy.act_dim), True),
+                 ("old_values", old_values, f32, (rows,), True), ("old_log_probs", old_log_probs, f32, (rows,), True),
+                 ("advantages", advantages, f32, (rows,), True), ("returns", returns, f32, (rows,), True))
+        check_tensors("DevicePPO", self.device, named)
         if B > self.max_batch:
             raise ValueError(f"DevicePPO: a minibatch of {B} samples, max_batch is {self.max_batch}")
-        return B, rows, [ptr(t) for _, t, _ in named]
+        return B, rows, [ptr(spec[1]) for spec in named]
 
     def _out(self, name, t, n):
         import torch
@@ -569,20 +573,50 @@ class DevicePPO(Handle):
         self._resolve()
         self._check_rc(self._L.mrp_ppo_begin_device(self._h, stream_of(self.device)))
 
-    def _minibatch(self, stream, B, index, rows, ptrs, normalize, target_kl, t, grad, stats):
-        """One ``mrp_ppo_minibatch_device`` on checked pointers; ``t`` is the step this would be."""
-        f, d = ctypes.c_float, ctypes.c_double
-        sc = adam_scalars(t, self.learning_rate, self.betas, self.eps)
-        cv = -1.0 if self.clip_range_vf is None else self.clip_range_vf
-        self._check_rc(self._L.mrp_ppo_minibatch_device(
-            self._h, stream, B, index, rows, *ptrs, 1 if normalize else 0, f(self.clip_range), f(cv),
-            d(-1.0 if target_kl is None else target_kl), f(self.ent_coef), d(self.vf_coef), d(self.max_grad_norm),
-            *[f(float(x)) for x in sc], grad, stats))
-        if index is not None or (normalize and B > 1):
-            self._staged = B
+    def _adam(self, t):
+        return [ctypes.c_float(float(x)) for x in adam_scalars(t, self.learning_rate, self.betas, self.eps)]
 
-    def _extended(self, old_values, index, normalize):
-        return old_values is not None or index is not None or normalize or self.clip_range_vf is not None
+    def _call(self, predicated, stream, B, index, rows, ptrs, normalize, target_kl, t, grad, stats):
+        """One minibatch on checked pointers: the gradient alone into ``grad``, or with ``grad`` None the
+        optimiser step that Adam counts as ``t``.  ``predicated``: ``mrp_ppo_minibatch_device`` under the progress
+        words (after ``_begin``); else ``mrp_ppo_step_device`` / ``mrp_ppo_grad_device``, which have no index, no
+        normalisation, no ``old_values`` and no ``target_kl``."""
+        f, d, L = ctypes.c_float, ctypes.c_double, self._L
+        if predicated:
+            self._check_rc(L.mrp_ppo_minibatch_device(
+                self._h, stream, B, index, rows, *ptrs, 1 if normalize else 0, f(self.clip_range), f(_or_off(self.clip_range_vf)),
+                d(_or_off(target_kl)), f(self.ent_coef), d(self.vf_coef), d(self.max_grad_norm), *self._adam(t), grad, stats))
+            if index is not None or (normalize and B > 1):
+                self._staged = B
+            return
+        head = (self._h, stream, B, *ptrs[:2], *ptrs[3:], f(self.clip_range), f(self.ent_coef), d(self.vf_coef))
+        if grad is not None:
+            self._check_rc(L.mrp_ppo_grad_device(*head, grad, stats))
+        else:
+            self._check_rc(L.mrp_ppo_step_device(*head, d(self.max_grad_norm), *self._adam(t), stats))
+
+    def _single(self, fields, old_values, index, normalize, out, stats_out, want_grad):
+        """``grad`` and ``step``: one checked minibatch through the unpredicated entry, or with any of
+        ``old_values``, ``index``, ``normalize`` and ``clip_range_vf`` through the predicated one."""
+        B, rows, ptrs = self._batch(*fields, old_values, index)
+        g = self._out("out", out, self.n_params) if want_grad else None
+        st = self._out("stats_out", stats_out, 5)
+        predicated = old_values is not None or index is not None or normalize or self.clip_range_vf is not None
+        if predicated:
+            self._begin()
+        self._call(predicated, stream_of(self.device), B, ptr(index), rows, ptrs, normalize, None, 1 if want_grad else self.t + 1,
+                   ptr(g), ptr(st))
+        if not want_grad:
+            self._t += 1
+        return g, st
+
+    def _finish(self, t0, n, target_kl):
+        """The bookkeeping after ``n`` enqueued minibatches from step count ``t0``: all applied without
+        ``target_kl``, else the device's progress words decide (``_resolve``)."""
+        if target_kl is None:
+            self._t, self._n_applied, self._stopped = t0 + n, n, False
+        else:
+            self._base, self._pending = t0, True
 
     def grad(self, obs, actions, old_log_probs, advantages, returns, out=None, stats_out=None, *, old_values=None, index=None,
              normalize=False):
@@ -593,38 +627,14 @@ class DevicePPO(Handle):
         ``old_values`` [B] is read under ``clip_range_vf``.  With ``index`` (int64 [B]) the fields hold any
         number of rows and the minibatch is rows ``index`` of them, gathered on the device; ``normalize``
         passes the advantages through ``normalize_adv_ref`` on the device first."""
-        B, rows, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns, old_values, index)
-        g, st = self._out("out", out, self.n_params), self._out("stats_out", stats_out, 5)
-        if self._extended(old_values, index, normalize):
-            self._begin()
-            self._minibatch(stream_of(self.device), B, ptr(index), rows, ptrs, normalize, None, 1, ptr(g), ptr(st))
-            return g, st
-        f = ctypes.c_float
-        del ptrs[2]
-        self._check_rc(self._L.mrp_ppo_grad_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
-                                                   ctypes.c_double(self.vf_coef), ptr(g), ptr(st)))
-        return g, st
+        return self._single((obs, actions, old_log_probs, advantages, returns), old_values, index, normalize, out, stats_out, True)
 
     def step(self, obs, actions, old_log_probs, advantages, returns, stats_out=None, *, old_values=None, index=None,
              normalize=False):
         """One optimiser step (``ppo_step_ref``) in place; returns the ``stats [5]`` device tensor.
         ``old_values``, ``index`` and ``normalize`` as in ``grad``.  ``target_kl`` belongs to ``train``:
         a ``step`` is always applied."""
-        B, rows, ptrs = self._batch(obs, actions, old_log_probs, advantages, returns, old_values, index)
-        st = self._out("stats_out", stats_out, 5)
-        if self._extended(old_values, index, normalize):
-            self._begin()
-            self._minibatch(stream_of(self.device), B, ptr(index), rows, ptrs, normalize, None, self._t + 1, None, ptr(st))
-            self._t += 1
-            return st
-        sc = adam_scalars(self.t + 1, self.learning_rate, self.betas, self.eps)
-        f = ctypes.c_float
-        del ptrs[2]
-        self._check_rc(self._L.mrp_ppo_step_device(self._h, stream_of(self.device), B, *ptrs, f(self.clip_range), f(self.ent_coef),
-                                                   ctypes.c_double(self.vf_coef), ctypes.c_double(self.max_grad_norm),
-                                                   *[f(float(x)) for x in sc], ptr(st)))
-        self._t += 1
-        return st
+        return self._single((obs, actions, old_log_probs, advantages, returns), old_values, index, normalize, None, stats_out, False)[1]
 
     def train(self, buffer, generator=None, poll=False):
         """``n_epochs`` passes over the buffer's shuffled minibatches (``buffer.get``'s ``randperm`` and
@@ -642,90 +652,74 @@ class DevicePPO(Handle):
         With an exchange (data-parallel training) every minibatch is the local phase into
         ``exchange.mine``, the exchange, and ``mrp_ppo_apply_device`` (``ppo_train_dist_ref``), in either
         gather mode.  Every rank must pass the same ``T * N``, ``batch_size`` and ``n_epochs``: they are
-        compared across ranks (one ``all_gather_object``, only when they differ from the last ones
+        compared across ranks (one ``dist.agree``, only when they differ from the last ones
         compared) and a mismatch raises ``ValueError`` on every rank before anything is enqueued."""
         import torch
-        total = buffer.n_steps * buffer.n_lanes
-        per_epoch = -(-total // self.batch_size)
-        stats = torch.zeros(self.n_epochs * per_epoch, 5, dtype=torch.float32, device=self.device)
-        u = 0
-        ex = self.exchange
+        total, bs = buffer.n_steps * buffer.n_lanes, self.batch_size
+        stats = torch.zeros(self.n_epochs * -(-total // bs), 5, dtype=torch.float32, device=self.device)
+        ex, kl, use_v, gather = self.exchange, self.target_kl, self.clip_range_vf is not None, self.minibatch == "device"
         if ex is not None:
             self._check_ranks(total)
-        if ex is None and self.minibatch == "torch" and self.clip_range_vf is None and self.target_kl is None:
-            for _ in range(self.n_epochs):
-                for obs, actions, _, old_lp, adv, ret in buffer.get(self.batch_size, generator):
-                    if self.normalize_advantage and adv.numel() > 1:
-                        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-                    self.step(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, stats_out=stats[u])
-                    u += 1
-            self._n_applied, self._stopped = u, False
-            return stats
-        self._begin()
-        t0, stream, kl = self._t, stream_of(self.device), self.target_kl
-        use_v = self.clip_range_vf is not None
+        # without an option, an exchange or the device gather a minibatch is one unpredicated mrp_ppo_step_device
+        predicated = ex is not None or gather or use_v or kl is not None
+        if predicated:
+            self._begin()
+        t0, stream, u = self.t, stream_of(self.device), 0
         if ex is None:
             def run(B, index, rows, ptrs, normalize):
-                self._minibatch(stream, B, index, rows, ptrs, normalize, kl, t0 + u + 1, None, stats[u].data_ptr())
+                self._call(predicated, stream, B, index, rows, ptrs, normalize, kl, t0 + u + 1, None, stats[u].data_ptr())
         else:
             # the local phase writes the gradient before clipping and the statistics side by side into exchange.mine
             P = self.n_params
             local_g, local_s = ex.mine[:P].data_ptr(), ex.mine[P:P + 5].data_ptr()
 
             def run(B, index, rows, ptrs, normalize):
-                self._minibatch(stream, B, index, rows, ptrs, normalize, None, 1, local_g, local_s)
+                self._call(True, stream, B, index, rows, ptrs, normalize, None, 1, local_g, local_s)
                 self._apply(stream, ex(), kl, t0 + u + 1, stats[u].data_ptr())
-        if self.minibatch == "device":
+        if gather:
             obs, actions, values, old_lp, adv, ret = buffer.flat_fields()
             _, rows, ptrs = self._batch(obs.reshape(total, -1), actions, old_lp, adv, ret, values if use_v else None,
                                         index=torch.zeros(1, dtype=torch.int64, device=self.device))
-        for _ in range(self.n_epochs):
-            if self.minibatch == "device":
+
+        def minibatches():
+            """One epoch's ``(B, index, rows, ptrs, normalize)``: slices of ``flat_index`` over the flat fields, or
+            ``buffer.get``'s gathered minibatches with torch's normalisation."""
+            if gather:
                 flat = buffer.flat_index(generator)
-                for start in range(0, total, self.batch_size):
-                    idx = flat[start:start + self.batch_size]
+                for start in range(0, total, bs):
+                    idx = flat[start:start + bs]
                     if idx.shape[0] > self.max_batch:
                         raise ValueError(f"DevicePPO: a minibatch of {idx.shape[0]} samples, max_batch is {self.max_batch}")
-                    run(int(idx.shape[0]), idx.data_ptr(), rows, ptrs, self.normalize_advantage)
-                    u += 1
+                    yield int(idx.shape[0]), idx.data_ptr(), rows, ptrs, self.normalize_advantage
             else:
-                for obs, actions, values, old_lp, adv, ret in buffer.get(self.batch_size, generator):
+                for obs, actions, values, old_lp, adv, ret in buffer.get(bs, generator):
                     if self.normalize_advantage and adv.numel() > 1:
                         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-                    B, rows, ptrs = self._batch(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, values if use_v else None)
-                    run(B, None, rows, ptrs, False)
-                    u += 1
+                    B, n, p = self._batch(obs.reshape(obs.shape[0], -1), actions, old_lp, adv, ret, values if use_v else None)
+                    yield B, None, n, p, False
+        for _ in range(self.n_epochs):
+            for mb in minibatches():
+                run(*mb)
+                u += 1
             if poll and kl is not None and self.progress()[0]:
                 break
-        if kl is None:
-            self._t, self._n_applied, self._stopped = t0 + u, u, False
-        else:
-            self._base, self._pending = t0, True
+        self._finish(t0, u, kl)
         return stats
 
     # ---- data-parallel training
     def _check_ranks(self, total):
-        """Every rank must enqueue the same number of minibatches: one ``all_gather_object`` of ``(T * N,
-        batch_size, n_epochs)``, repeated only when the triple changes."""
+        """Every rank must enqueue the same number of minibatches: ``dist.agree`` on ``(T * N, batch_size,
+        n_epochs)``, repeated only when the triple changes."""
         triple = (int(total), self.batch_size, self.n_epochs)
-        if triple == self._checked:
-            return
-        ex = self.exchange
-        if ex.world > 1:
-            import torch.distributed as dist
-            seen = [None] * ex.world
-            dist.all_gather_object(seen, triple, group=ex.group)
-            if any(tuple(t) != tuple(seen[0]) for t in seen):
-                raise ValueError(f"DevicePPO.train: (T * N, batch_size, n_epochs) differs across ranks: {seen}")
-        self._checked = triple
+        if triple != self._checked:
+            agree("DevicePPO.train", "(T * N, batch_size, n_epochs)", triple, self.exchange.world, self.exchange.group)
+            self._checked = triple
 
     def _apply(self, stream, parts, target_kl, t, stats):
         """One ``mrp_ppo_apply_device`` on a checked ``[R, stride]`` tensor; ``t`` is the step this would be."""
-        f, d = ctypes.c_float, ctypes.c_double
-        sc = adam_scalars(t, self.learning_rate, self.betas, self.eps)
+        d = ctypes.c_double
         self._check_rc(self._L.mrp_ppo_apply_device(self._h, stream, int(parts.shape[0]), parts.data_ptr(), int(parts.shape[1]),
-                                                    d(-1.0 if target_kl is None else target_kl), d(self.max_grad_norm),
-                                                    *[f(float(x)) for x in sc], stats))
+                                                    d(_or_off(target_kl)), d(self.max_grad_norm), *self._adam(t), stats))
 
     def apply(self, parts, stats_out=None):
         """The apply phase alone (``combine_ref``, then ``kl_stop_ref`` and ``adam_ref`` on the combined
@@ -743,10 +737,7 @@ class DevicePPO(Handle):
         self._begin()
         t0 = self._t
         self._apply(stream_of(self.device), parts, self.target_kl, t0 + 1, ptr(st))
-        if self.target_kl is None:
-            self._t, self._n_applied, self._stopped = t0 + 1, 1, False
-        else:
-            self._base, self._pending = t0, True
+        self._finish(t0, 1, self.target_kl)
         return st
 
     def set_state(self, m, v, t):
@@ -764,20 +755,14 @@ class DevicePPO(Handle):
         rank, so that the replicas start equal (synchronises; every rank's policy must hold parameters of
         the one architecture already).  The tensors travel on the device under an nccl group and on the
         host otherwise."""
-        import torch
-        import torch.distributed as dist
         like = self.policy.get_params()
         m, v = self.state()
         P, A = self.n_params, self.policy.act_dim
-        buf = torch.from_numpy(np.concatenate([flatten_params(like), like.std, m, v]).astype(_f32))
-        step = torch.tensor([self.t], dtype=torch.int64)
-        if dist.get_backend(group) == "nccl":
-            buf, step = buf.to(self.device), step.to(self.device)
-        dist.broadcast(buf, src, group=group)
-        dist.broadcast(step, src, group=group)
-        a = buf.cpu().numpy()
+        mine, step = np.concatenate([flatten_params(like), like.std, m, v]).astype(_f32), np.array([self.t], np.int64)
+        a = broadcast_array(mine, src, group, self.device)
+        step = broadcast_array(step, src, group, self.device)       # an int64 of its own: float32 holds 24 bits
         self.policy.set_params(unflatten_params(like, a[:P], std=a[P:P + A].copy()))
-        self.set_state(a[P + A:2 * P + A], a[2 * P + A:], int(step.item()))
+        self.set_state(a[P + A:2 * P + A], a[2 * P + A:], int(step[0]))
 
     def staged(self):
         """Host copies of the staging buffers as the last gathered or device-normalised minibatch left

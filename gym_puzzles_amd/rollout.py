@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._device import check_tensor, index_of, ptr, stream_of
+from ._device import check_tensor, check_tensors, index_of, ptr, stream_of
 
 
 def gae_ref(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, truncated=None, terminal_values=None):
@@ -111,10 +111,8 @@ def collect_rollouts(env, policy, buffer, obs, episode_start, norm=None, eps_out
     N, T, dev = buffer.n_lanes, buffer.n_steps, buffer.device
     O, A = policy.obs_dim, policy.act_dim
     f32, u8 = torch.float32, torch.uint8
-    check_tensor("collect_rollouts", "obs", obs, dev, f32, (N, O))
-    check_tensor("collect_rollouts", "episode_start", episode_start, dev, u8, (N,))
-    if eps_out is not None:
-        check_tensor("collect_rollouts", "eps_out", eps_out, dev, f32, (T, N, A))
+    check_tensors("collect_rollouts", dev, (("obs", obs, f32, (N, O), False), ("episode_start", episode_start, u8, (N,), False),
+                                            ("eps_out", eps_out, f32, (T, N, A), True)))
     if tuple(buffer.obs_shape) != (O,) or buffer.act_dim != A:
         raise ValueError(f"collect_rollouts: the buffer holds obs {buffer.obs_shape} / {buffer.act_dim} actions, "
                          f"the policy takes ({O},) / {A}")

@@ -30,7 +30,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._device import Handle, check_tensor, ptr, stream_of
+from ._device import Handle, check_tensor, check_tensors, ptr, stream_of
+from .dist import agree, broadcast_array
 from ._native import ENV_IDS, STATUS_FAULT, STATUS_NONFINITE, Batch, env_dims
 from .spawn import ENV_CFG, V2_AGENT_IDS, V3_AGENT_IDS
 from .pixels import stack_shape
@@ -210,12 +211,10 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
         dev = torch.device("cuda", self.device)
         N, O, A = self.num_envs, self._b.obs_dim, self._b.act_dim
         f32, u8 = torch.float32, torch.uint8
-        for name, t, dt, shape, optional in (
-                ("actions", actions, f32, (N, A), True), ("obs", obs, f32, (N, O), False), ("reward", reward, f32, (N,), False),
-                ("done", done, u8, (N,), False), ("truncated", truncated, u8, (N,), True), ("status", status, u8, (N,), True),
-                ("terminal_obs", terminal_obs, f32, (N, O), True), ("reward64", reward64, torch.float64, (N,), True)):
-            if t is not None or not optional:
-                check_tensor("step_torch", name, t, dev, dt, shape)
+        check_tensors("step_torch", dev, (
+            ("actions", actions, f32, (N, A), True), ("obs", obs, f32, (N, O), False), ("reward", reward, f32, (N,), False),
+            ("done", done, u8, (N,), False), ("truncated", truncated, u8, (N,), True), ("status", status, u8, (N,), True),
+            ("terminal_obs", terminal_obs, f32, (N, O), True), ("reward64", reward64, torch.float64, (N,), True)))
         self._b.set_stream(stream_of(dev))
         self._b.step_device(ptr(actions), ptr(obs), ptr(reward), ptr(done), ptr(truncated), ptr(status), ptr(terminal_obs),
                             ptr(reward64))
@@ -233,9 +232,8 @@ class MultiRobotPuzzleVecEnv(_VecEnvBase):
         import torch
         dev = torch.device("cuda", self.device)
         shape = (self.num_envs,) + tuple(self.observation_space.shape)
-        for name, t, want in (("done", done, (self.num_envs,)), ("out", out, shape)):
-            if t is not None:
-                check_tensor("pixels_torch", name, t, dev, torch.uint8, want)
+        u8 = torch.uint8
+        check_tensors("pixels_torch", dev, (("done", done, u8, (self.num_envs,), True), ("out", out, u8, shape, True)))
         if out is None:
             if self._pair is None:
                 self._pair = [torch.zeros(shape, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -324,7 +322,7 @@ class DeviceVecNormalize(Handle):
     ``training`` off nothing is exchanged.  The discounted returns and Monitor stay per lane.  ``group``,
     ``host_stage`` and ``force_collective`` are ``GradExchange``'s, for the exchange built from ``shard``.  Every
     rank must hold the same ``(n_lanes, obs_dim, training, norm_obs)``: the first call after construction or after
-    a change of the two flags compares them across ranks (one ``all_gather_object``) and raises ``ValueError`` on
+    a change of the two flags compares them across ranks (one ``dist.agree``) and raises ``ValueError`` on
     every rank on a mismatch, before anything is enqueued.  Use ``sync_from`` after ``set_stats`` on one rank."""
 
     _DESTROY, _LAST_ERROR = "mrp_norm_destroy", "mrp_norm_last_error"
@@ -354,63 +352,42 @@ class DeviceVecNormalize(Handle):
             check_tensor("DeviceVecNormalize", "exchange.mine", exchange.mine, self._dev, torch.float64, (exchange.part_stride,))
         self.exchange = exchange
 
-    def _launch(self, who, tensors, call, *args):
-        """Check every given tensor of ``tensors`` (name, tensor, dtype, shape, optional), then launch."""
-        for name, t, dtype, shape, optional in tensors:
-            if t is not None or not optional:
-                check_tensor(who, name, t, self._dev, dtype, shape)
-        self._check_rc(self._L.mrp_norm_set_stream(self._h, stream_of(self._dev)))
-        self._check_rc(call(self._h, *args))
-
-    def _launch_dist(self, who, tensors, step, obs, reward, *rest):
-        """The data-parallel form of ``_launch``: local phase, exchange, apply phase when statistics move,
-        else the plain call (no collective); ``rest`` are the arguments of ``mrp_norm_apply_device`` after
-        ``d_reward``."""
-        for name, t, dtype, shape, optional in tensors:
-            if t is not None or not optional:
-                check_tensor(who, name, t, self._dev, dtype, shape)
-        self._check_ranks(who)
+    def _launch(self, who, tensors, step, obs, reward, *rest):
+        """Check every tensor of ``tensors`` (``check_tensors``' specs), then launch on the current torch stream:
+        with an exchange and statistics to move the local phase, the exchange and the apply phase, else the
+        plain entry (no collective).  ``rest`` are ``mrp_norm_apply_device``'s arguments after ``d_reward``."""
+        check_tensors(who, self._dev, tensors)
         L, ex = self._L, self.exchange
+        if ex is not None:
+            self._check_ranks(who)
         self._check_rc(L.mrp_norm_set_stream(self._h, stream_of(self._dev)))
-        if not (self._training and (self._norm_obs or step)):
-            if step:
-                return self._check_rc(L.mrp_norm_step_device_ex(self._h, obs, reward, *rest))
-            return self._check_rc(L.mrp_norm_reset_device(self._h, obs, rest[3]))
-        self._check_rc(L.mrp_norm_local_device(self._h, obs, reward, step, ex.mine.data_ptr()))
-        parts = ex()
-        self._check_rc(L.mrp_norm_apply_device(self._h, int(parts.shape[0]), parts.data_ptr(), int(parts.shape[1]), step, obs,
-                                               reward, *rest))
+        if ex is not None and self._training and (self._norm_obs or step):
+            self._check_rc(L.mrp_norm_local_device(self._h, obs, reward, step, ex.mine.data_ptr()))
+            parts = ex()
+            self._check_rc(L.mrp_norm_apply_device(self._h, int(parts.shape[0]), parts.data_ptr(), int(parts.shape[1]), step, obs,
+                                                   reward, *rest))
+        elif step:
+            self._check_rc(L.mrp_norm_step_device_ex(self._h, obs, reward, *rest))
+        else:
+            self._check_rc(L.mrp_norm_reset_device(self._h, obs, rest[3]))
 
     def _check_ranks(self, who):
-        """The ranks must take the same branch, or the collective hangs: one ``all_gather_object`` of
-        ``(n_lanes, obs_dim, training, norm_obs)``, repeated only when the tuple changes."""
+        """The ranks must take the same branch, or the collective hangs: ``dist.agree`` on ``(n_lanes, obs_dim,
+        training, norm_obs)``, repeated only when the tuple changes."""
         mine = (int(self.n_lanes), int(self.obs_dim), self._training, self._norm_obs)
-        if mine == self._checked:
-            return
-        ex = self.exchange
-        if ex.world > 1:
-            import torch.distributed as dist
-            seen = [None] * ex.world
-            dist.all_gather_object(seen, mine, group=ex.group)
-            if any(tuple(t) != tuple(seen[0]) for t in seen):
-                raise ValueError(f"{who}: (n_lanes, obs_dim, training, norm_obs) differs across ranks: {seen}")
-        self._checked = mine
+        if mine != self._checked:
+            agree(who, "(n_lanes, obs_dim, training, norm_obs)", mine, self.exchange.world, self.exchange.group)
+            self._checked = mine
 
     def sync_from(self, src=0, group=None):
         """Broadcast rank ``src``'s statistics and load them on every rank (after ``set_stats`` / a load on
         one rank, or on resume; synchronises).  The vector travels on the device under an nccl group and on
         the host otherwise; ``group`` defaults to the exchange's."""
-        import torch
-        import torch.distributed as dist
         if group is None and self.exchange is not None:
             group = self.exchange.group
         st = np.zeros(2 * self.obs_dim + 4, np.float64)
         self._check_rc(self._L.mrp_norm_get_stats(self._h, st.ctypes.data))
-        buf = torch.from_numpy(st)
-        if dist.get_backend(group) == "nccl":
-            buf = buf.to(self._dev)
-        dist.broadcast(buf, src, group=group)
-        st = np.ascontiguousarray(buf.cpu().numpy())
+        st = broadcast_array(st, src, group, self._dev)
         self._check_rc(self._L.mrp_norm_set_stats(self._h, st.ctypes.data))
 
     @property
@@ -437,10 +414,7 @@ class DeviceVecNormalize(Handle):
         import torch
         shape = (self.n_lanes, self.obs_dim)
         tensors = (("obs", obs, torch.float32, shape, False), ("obs_out", obs_out, torch.float32, shape, False))
-        if self.exchange is not None:
-            return self._launch_dist("DeviceVecNormalize.reset", tensors, 0, ptr(obs), None, None, None, None, ptr(obs_out),
-                                     None, None, None, None)
-        self._launch("DeviceVecNormalize.reset", tensors, self._L.mrp_norm_reset_device, ptr(obs), ptr(obs_out))
+        self._launch("DeviceVecNormalize.reset", tensors, 0, ptr(obs), None, None, None, None, ptr(obs_out), None, None, None, None)
 
     def step(self, obs, reward, done, obs_out, reward_out, term_obs=None, term_out=None, ep_return=None, ep_len=None,
              reward64=None):
@@ -455,11 +429,8 @@ class DeviceVecNormalize(Handle):
                    ("term_obs", term_obs, f32, NO, True), ("term_out", term_out, f32, NO, True),
                    ("ep_return", ep_return, f64, N, True), ("ep_len", ep_len, torch.int32, N, True),
                    ("reward64", reward64, f64, N, True))
-        if self.exchange is not None:
-            return self._launch_dist("DeviceVecNormalize.step", tensors, 1, ptr(obs), ptr(reward), ptr(reward64), ptr(done),
-                                     ptr(term_obs), ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
-        self._launch("DeviceVecNormalize.step", tensors, self._L.mrp_norm_step_device_ex, ptr(obs), ptr(reward), ptr(reward64),
-                     ptr(done), ptr(term_obs), ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
+        self._launch("DeviceVecNormalize.step", tensors, 1, ptr(obs), ptr(reward), ptr(reward64), ptr(done), ptr(term_obs),
+                     ptr(obs_out), ptr(reward_out), ptr(term_out), ptr(ep_return), ptr(ep_len))
 
     def get_stats(self) -> dict:
         st = np.zeros(2 * self.obs_dim + 4, np.float64)

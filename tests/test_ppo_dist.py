@@ -242,12 +242,12 @@ def _worker(rank, world, port, force, q):
         dist.destroy_process_group()
 
 
-def _spawn(world, force):
+def _spawn(world, force, target=None):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, force, q)) for r in range(world)]
+    procs = [ctx.Process(target=target or _worker, args=(r, world, port, force, q)) for r in range(world)]
     for p in procs:
         p.start()
     results = []
@@ -286,6 +286,56 @@ def test_grad_exchange_world_one():
         GradExchange(Shard(0, 1, 4), 0, "cpu")
     (rank, stride, forced), = _spawn(1, True)                       # the collective itself at world size 1
     assert rank == 0 and stride == 128 and np.array_equal(forced[0, :N_FLOATS], _block(0) + 1)
+
+
+# ---- agree and broadcast_array -----------------------------------------------------------------------
+def _bits_vector():
+    """float64 values whose bits a conversion on the way would change: a denormal-range magnitude float32 cannot
+    hold, -0.0, a NaN with a payload, and a value with all 52 fraction bits in use."""
+    return np.array([0x7FF8000000ABCDEF, 0x8000000000000000, 0x3FF5555555555555], np.uint64).view(np.float64).tolist() + [1e-300, -1e300]
+
+
+def _helpers_worker(rank, world, port, _, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+
+    from gym_puzzles_amd.dist import agree, broadcast_array
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        assert agree("who", "(a, b)", (3, "x"), world) is None            # equal values return
+        try:
+            agree("who", "(a, rank)", (3, rank), world)
+            msg = None
+        except ValueError as e:
+            msg = str(e)
+        mine = np.array(_bits_vector(), np.float64).view(np.uint64) if rank == 0 else np.full(5, 7, np.uint64)
+        vec = mine.copy().view(np.float64)
+        got = broadcast_array(vec, 0, None, "cpu")
+        assert got.dtype == np.float64 and np.array_equal(vec.view(np.uint64), mine), "the caller's array is not written"
+        q.put((rank, msg, got.view(np.uint64).copy()))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_agree_and_broadcast_array_two_gloo_ranks():
+    results = _spawn(2, False, target=_helpers_worker)
+    assert sorted(r for r, _, _ in results) == [0, 1]
+    want = np.array(_bits_vector(), np.float64).view(np.uint64)
+    for _, msg, got in results:
+        assert msg == "who: (a, rank) differs across ranks: [(3, 0), (3, 1)]", "raised on every rank, with both values"
+        assert np.array_equal(got, want), "rank 0's float64 vector bit for bit"
+
+
+def test_agree_world_one_makes_no_collective(monkeypatch):
+    import torch.distributed as dist
+
+    from gym_puzzles_amd.dist import agree
+    calls = []
+    monkeypatch.setattr(dist, "all_gather_object", lambda *a, **k: calls.append(1))
+    assert not dist.is_initialized()
+    assert agree("who", "(a, b)", (1, 2), 1) is None and calls == []
 
 
 def test_names_and_abi_of_the_dist_path():

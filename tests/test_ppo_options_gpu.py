@@ -288,6 +288,38 @@ def test_target_kl_never_reached_and_with_clip_range_vf(gpu_lib):
     pol.close()
 
 
+@pytest.mark.parametrize("mode", ["torch", "device"])
+def test_train_without_options_after_a_stop(gpu_lib, mode):
+    """A train() that stops at its first minibatch leaves ``stopped = 1`` in the device's progress words.  With
+    ``target_kl`` then switched off on the same object, the next train() (with "torch" the unpredicated
+    mrp_ppo_step_device, which has no begin to clear the words) applies every minibatch and equals
+    ppo_train_ref bitwise.  Heads-only policy, a 4 x 8 buffer, two minibatches of 16."""
+    import torch
+
+    from gym_puzzles_amd import DeviceRolloutBuffer
+    T, N, bs, lr = 4, 8, 16, 1e-3
+    params = make_params(ARCHS["heads-only"], seed=1)
+    obs, actions, old, adv, ret = make_batch(params, T * N, seed=9)     # moved log-probs: every approx_kl term is > 0
+    buf = DeviceRolloutBuffer(T, N, (params.obs_dim,), params.act_dim, device=0)
+    _fill(buf, (obs, actions, P.values_ref(params, obs), old, adv, ret))
+    pol = P.DevicePolicy.from_params(params)
+    ppo = R.DevicePPO(pol, learning_rate=lr, n_epochs=1, batch_size=bs, normalize_advantage=False, target_kl=0.0, minibatch=mode, **HP)
+    ppo.train(buf, generator=_gen(7))
+    assert (ppo.stopped, ppo.n_applied, ppo.t) == (True, 0, 0)
+    _same(R.flatten_params(pol.get_params()), R.flatten_params(params), "the stopped call applies nothing")
+    ppo.target_kl = None
+    stats = ppo.train(buf, generator=_gen(11))
+    assert (ppo.n_applied, ppo.t, ppo.stopped) == (2, 2, False)
+    perm = torch.randperm(T * N, generator=_gen(11)).numpy()
+    state = R.AdamState(R.flatten_params(params).size)
+    want, want_stats = R.ppo_train_ref(params, state, (obs, actions, old, adv, ret), [(perm % T) * N + perm // T], bs, lr=lr,
+                                       normalize_advantage=False, **HP)
+    _same(stats, want_stats, f"{mode}: statistics")
+    _same_run(_snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), f"{mode}: after the stop")
+    ppo.close()
+    pol.close()
+
+
 # ---- argument errors ---------------------------------------------------------------------------------
 def test_option_argument_errors(gpu_lib):
     import torch
