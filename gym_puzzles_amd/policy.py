@@ -171,6 +171,33 @@ def check_arch(obs_dim, act_dim, n_shared, n_pi, n_vf, widths):
             raise ValueError(f"policy: layer width {w} outside 1..{MAX_WIDTH}")
 
 
+def random_params(obs_dim, act_dim, shared, pi, vf, activation, seed, bias_scale, log_std, negzero_bias=False):
+    """A synthetic network for tests and benches: towers of the widths ``shared`` / ``pi`` / ``vf``, drawn
+    from ``np.random.default_rng(seed)`` layer by layer (trunk, policy tower, value tower, action head,
+    value head), per layer the weights ``N(0, 1 / in)`` and then the bias ``N(0, bias_scale^2)``.
+    ``negzero_bias`` makes every weight negative and every bias -0: a row of +0 then gives products of
+    -0, which leave a bias of -0 alone."""
+    rng = np.random.default_rng(seed)
+
+    def lin(k, n):
+        w = (rng.standard_normal((n, k)) / np.sqrt(k)).astype(_f32)
+        b = (rng.standard_normal(n) * bias_scale).astype(_f32)
+        if negzero_bias:
+            w, b = -np.abs(w), np.full(n, -0.0, _f32)
+        return w, b
+
+    def tower(k, widths):
+        out = []
+        for n in widths:
+            out.append(lin(k, n))
+            k = n
+        return out, k
+    s, kt = tower(obs_dim, shared)
+    p, kp = tower(kt, pi)
+    v, kv = tower(kt, vf)
+    return PolicyParams(s, p, v, lin(kp, act_dim), lin(kv, 1), log_std, activation)
+
+
 def params_from_state_dict(sd, activation="tanh"):
     """``PolicyParams`` from an SB3 ``ActorCriticPolicy`` ``state_dict`` (torch tensors or arrays):
     ``mlp_extractor.{shared_net,policy_net,value_net}.N.{weight,bias}`` in ascending ``N``,

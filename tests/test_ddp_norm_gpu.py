@@ -19,36 +19,20 @@ in it: the ranks are started (fork + exec of a fresh interpreter) before this pr
 from __future__ import annotations
 
 import json
-import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
-
 import vecnorm_exact as ve
+from ranks import torchrun
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAT_KEYS = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _launch(tmp_path, *extra):
-    plan, out = tmp_path / "plan.json", tmp_path / "ranks"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tools", "norm_ddp_worker.py"), "--plan", str(plan),
-           "--out", str(out), *extra]
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
-    return r, out
+    out = tmp_path / "ranks"
+    torchrun("tools/norm_ddp_worker.py", 2, "--plan", tmp_path / "plan.json", "--out", out, *extra,
+             env=dict(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0"))
+    return out
 
 
 def _stats_dict(vec, D):
@@ -94,8 +78,7 @@ def test_two_ranks_hold_one_set_of_statistics(tmp_path):
     from vecnorm_dist import column0, replay_update
     cases = _cases()
     _write_plan(tmp_path, cases)
-    r, out = _launch(tmp_path)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    out = _launch(tmp_path)
     ranks = [np.load(out / f"rank{k}.npz") for k in range(2)]
     # sync_from(0): rank 1 started from the initial statistics and holds rank 0's loaded ones afterwards, bit for bit
     a, b = ranks
@@ -133,10 +116,9 @@ def test_two_ranks_hold_one_set_of_statistics(tmp_path):
             t += 1
         assert t == len(calls)
         # (c) the exact rule over all 2 L lanes
-        clips = (args.get("clip_obs", 10.0), args.get("clip_reward", 10.0))
         if i != 1:
             exact = ve.exact_records(("ddp", i), inputs, args, script)
-            worst = ve.judge(got, exact, *clips, where=f"case {i}")
+            worst = ve.judge(got, exact, *ve.clips(args), where=f"case {i}")
             print(f"two ranks, case {i}, worst error / bound:", {k: float(f"{v:.3g}") for k, v in worst.items()})
             continue
         # the non-finite case: NaN exactly where numpy's rule over the 130 lanes has it, on rank 0's lanes too;
@@ -169,8 +151,7 @@ def test_ranks_that_disagree_on_norm_obs_both_raise(tmp_path):
     """(d): rank 1 has norm_obs off.  The agreement check raises ValueError on both ranks before anything is
     enqueued; both exit (the launch has its own time limit, and the ranks' process group one of 60 s)."""
     _write_plan(tmp_path, [])
-    r, out = _launch(tmp_path, "--mismatch")
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    out = _launch(tmp_path, "--mismatch")
     for k in range(2):
         msg = (out / f"mismatch{k}.txt").read_text()
         assert "DeviceVecNormalize.reset" in msg and "differs across ranks" in msg and "True" in msg and "False" in msg, msg

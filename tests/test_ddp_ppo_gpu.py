@@ -13,52 +13,29 @@ it: the ranks are started (fork + exec of a fresh interpreter) before this proce
 """
 from __future__ import annotations
 
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+from ppo_cases import ARCHS, bits, make_params
+from ranks import torchrun
 
 
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_two_ranks_train_identically_and_equal_the_rule(tmp_path):
-    from test_ppo import ARCHS, make_params
-
     from gym_puzzles_amd import ppo as R
     out = tmp_path / "ranks"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tools", "ppo_ddp_worker.py"), "--out", str(out)]
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    torchrun("tools/ppo_ddp_worker.py", 2, "--out", out, env=dict(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0"))
     ranks = [np.load(out / f"rank{k}.npz") for k in range(2)]
     a, b = ranks
     assert int(a["lane_offset"]) == 0 and int(b["lane_offset"]) == 8
     # sync_from: both ranks start from rank 0's parameters, std, moments and step count
     for key in ("flat0", "std0", "m0", "v0"):
-        assert np.array_equal(_bits(a[key]), _bits(b[key])), key
+        assert np.array_equal(bits(a[key]), bits(b[key])), key
     assert int(a["t0"]) == int(b["t0"]) == 3 and a["m0"].any() and a["v0"].any()
     # the ranks' rollouts differ (their own lanes, their own noise), their final states do not
     assert not np.array_equal(a["obs"], b["obs"]) and not np.array_equal(a["perms"], b["perms"])
     for key in ("flat", "std", "m", "v", "stats"):
-        assert np.array_equal(_bits(a[key]), _bits(b[key])), f"the ranks' {key} differ"
+        assert np.array_equal(bits(a[key]), bits(b[key])), f"the ranks' {key} differ"
     assert int(a["t"]) == int(b["t"]) == 3 + 8 and int(a["n_applied"]) == int(b["n_applied"]) == 8
     assert int(a["stopped"]) == int(b["stopped"]) == 0
     assert a["stats"].shape == (8, 5) and not np.array_equal(a["flat"], a["flat0"])
@@ -74,5 +51,5 @@ def test_two_ranks_train_identically_and_equal_the_rule(tmp_path):
     assert state.t == 11
     for got, ref, what in ((a["stats"], want_stats, "statistics"), (a["flat"], R.flatten_params(want), "parameters"),
                            (a["std"], want.std, "std"), (a["m"], state.m, "m"), (a["v"], state.v, "v")):
-        bad = np.flatnonzero(_bits(got).ravel() != _bits(ref).ravel())
+        bad = np.flatnonzero(bits(got).ravel() != bits(ref).ravel())
         assert bad.size == 0, f"{what}: {bad.size} of {ref.size} differ from ppo_train_dist_ref, first at {bad[:5]}"

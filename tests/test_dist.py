@@ -8,24 +8,14 @@ nothing about any lane.
 from __future__ import annotations
 
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from ranks import ROOT, spawn
 
 
-def _worker(rank, world, port, lanes_per_rank, steps, to_all, q, force=False):
+def _worker(rank, world, port, lanes_per_rank, steps, to_all, force, q):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
@@ -60,21 +50,10 @@ def _worker(rank, world, port, lanes_per_rank, steps, to_all, q, force=False):
 
 @pytest.mark.parametrize("to_all", [False, True])
 def test_two_rank_gather_equals_single_process(oracle_lib, to_all):
-    import torch.multiprocessing as mp
-
     from gym_puzzles_amd.spawn import draw_bounds
     from oracle.oracle import batch_run
     world, L, steps = 2, 6, 80
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, L, steps, to_all, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=240) for _ in range(world if to_all else 1)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    results = spawn(_worker, world, L, steps, to_all, False, n_results=world if to_all else 1)
     _, _, bodies, rsum, eps = batch_run(0, world * L, steps, 17, draw_bounds(0), threads=2, outputs=True)
     for rank, ob, rw, dn in results:
         assert rank == 0 or to_all
@@ -87,18 +66,11 @@ def test_two_rank_gather_equals_single_process(oracle_lib, to_all):
 def test_forced_collective_world_one(oracle_lib, to_all):
     """bench.py --force-collective at world size 1 (the one-GPU RCCL rehearsal) on gloo: the gather
     runs through torch.distributed and returns the rank's own rows unchanged."""
-    import torch.multiprocessing as mp
-
     from gym_puzzles_amd.spawn import draw_bounds
     from oracle.oracle import batch_run
     L, steps = 6, 40
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_worker, args=(0, 1, _free_port(), L, steps, to_all, q, True))
-    p.start()
-    rank, ob, rw, dn = q.get(timeout=240)
-    p.join(timeout=60)
-    assert p.exitcode == 0 and rank == 0
+    (rank, ob, rw, dn), = spawn(_worker, 1, L, steps, to_all, True)
+    assert rank == 0
     _, _, bodies, rsum, eps = batch_run(0, L, steps, 17, draw_bounds(0), threads=1, outputs=True)
     assert np.array_equal(ob, bodies) and np.array_equal(rw, rsum.astype(np.float32)) and np.array_equal(dn, eps > 1)
 

@@ -20,22 +20,14 @@ from __future__ import annotations
 
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+from ranks import ROOT, torchrun
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+RANK_ENV = dict(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
 
 
 def _one_batch_rows(env_id, lanes, W, K):
@@ -94,13 +86,8 @@ def test_bench_rccl_gather_one_rank(tmp_path):
     process's batch bit for bit."""
     W, K, lanes = 2, 6, 256
     dump = tmp_path / "gather.npy"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-backend", "nccl",
-           "--force-collective", "--env", "0", "--lanes", str(lanes), "--steps", str(K), "--warmup", str(W),
-           "--no-cpu-baseline", "--dump-gather", str(dump)]
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r = torchrun("bench.py", 1, "--gpus", "1", "--dist-backend", "nccl", "--force-collective", "--env", "0", "--lanes", lanes,
+                 "--steps", K, "--warmup", W, "--no-cpu-baseline", "--dump-gather", dump, env=RANK_ENV)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     line = json.loads(lines[0])
@@ -119,13 +106,8 @@ def test_bench_rccl_gather_one_rank(tmp_path):
 def test_bench_two_ranks_gather_equals_one_batch(tmp_path, env_id, lanes):
     W, K = 2, 6
     dump = tmp_path / "gather.npy"
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--same-device", "--env", str(env_id), "--lanes", str(lanes), "--steps", str(K), "--warmup", str(W),
-           "--no-cpu-baseline", "--dump-gather", str(dump)]
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r = torchrun("bench.py", 2, "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--env", env_id, "--lanes", lanes,
+                 "--steps", K, "--warmup", W, "--no-cpu-baseline", "--dump-gather", dump, env=RANK_ENV)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "rank 0 (only) prints one JSON line"
     line = json.loads(lines[0])

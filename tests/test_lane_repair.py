@@ -11,27 +11,12 @@ same repair end to end.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
-import pytest
-
-from test_packed import _hipcc
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+import hostprog
 
 
 def test_contact_slot_rule_and_mark_repair(tmp_path):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    exe = tmp_path / "lane_repair_check"
-    from gym_puzzles_amd.build import FLAGS
     # the library's flags, host side only (no device code in the check)
-    flags = [f for f in FLAGS if not f.startswith("--offload-arch") and f != "-fPIC"]
-    subprocess.run([hipcc, *flags, "-x", "hip", "--cuda-host-only", os.path.join(HERE, "lane_repair_check.cpp"), "-o", str(exe)],
-                   check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostprog.run(hostprog.build("lane_repair_check.cpp", tmp_path / "lane_repair_check", hostprog.library_flags()))
     print(r.stdout)
     lines = dict((ln.split()[0], (int(ln.split()[1]), int(ln.split()[2])))
                  for ln in r.stdout.strip().splitlines() if not ln.startswith("#"))

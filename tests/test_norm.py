@@ -305,10 +305,6 @@ def _exact():
     return vecnorm_exact
 
 
-def _clips(args):
-    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
-
-
 def _runs():
     """(id, inputs, constructor arguments, script, exact records) of every case and scenario."""
     ve = _exact()
@@ -328,7 +324,7 @@ def test_restatement_is_within_the_exact_bounds():
     worst = dict.fromkeys(ve.RATIO_KEYS, 0.0)
     for name, inputs, args, script, exact in _runs():
         got = ve.run_script(ve.RefAdapter(VecNormalizeRef(inputs["L"], inputs["D"], **args)), inputs, script)
-        w = ve.judge(got, exact, *_clips(args), where=name)
+        w = ve.judge(got, exact, *ve.clips(args), where=name)
         worst = {k: max(worst[k], w[k]) for k in worst}
     print("restatement, worst error / bound:", {k: float(f"{v:.3g}") for k, v in worst.items()})
     for k in ("obs_mean", "obs_var", "ret_mean", "ret_var", "obs_slack", "reward_slack", "term_slack"):
@@ -423,7 +419,7 @@ def test_checkers_reject_a_wrong_rule(kind):
     rejected = []
     for name, inputs, args, script, exact in _runs():
         got = ve.run_script(ve.RefAdapter(_make_wrong(kind, inputs["L"], inputs["D"], args)), inputs, script)
-        w = ve.judge(got, exact, *_clips(args), fail=False, where=name)
+        w = ve.judge(got, exact, *ve.clips(args), fail=False, where=name)
         if max(w[k] for k in w if not k.endswith("_slack")) > 1.0:
             rejected.append(name)
     print(f"{kind}: rejected on {len(rejected)} runs: {rejected}")

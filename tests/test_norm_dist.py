@@ -12,27 +12,17 @@ not tested against these bounds.
 from __future__ import annotations
 
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
-
 import vecnorm_exact as ve
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ppo_cases import bits
+from ranks import ROOT, spawn
 
 # (lanes per rank, columns, constructor arguments)
 SHAPES = [(1, 1, "default"), (1, 28, "clipped"), (2, 3, "gamma1"), (63, 5, "default"), (64, 7, "clipped"), (257, 28, "default")]
 STAT_KEYS = ("obs_mean", "obs_var", "ret_mean", "ret_var", "obs_slack", "reward_slack", "term_slack")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def _clips(args):
-    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
 
 
 def _dist(R, L, D, **args):
@@ -50,7 +40,7 @@ def test_rule_is_within_the_exact_bounds(R, shape):
     inputs = ve.make_inputs(R * L, D, 4000 + 100 * R + SHAPES.index(shape))
     exact = ve.exact_records(("dist", R, shape), inputs, args, ve.plain_script())
     got = ve.run_script(ve.RefAdapter(_dist(R, L, D, **args)), inputs, ve.plain_script())
-    w = ve.judge(got, exact, *_clips(args), where=f"R{R}-{ve.case_id(shape)}")
+    w = ve.judge(got, exact, *ve.clips(args), where=f"R{R}-{ve.case_id(shape)}")
     print(f"dist rule R={R} {ve.case_id(shape)}, worst error / bound:", {k: float(f"{v:.3g}") for k, v in w.items()})
     for k in STAT_KEYS:
         assert w[k] < 0.5, (k, w[k])
@@ -69,7 +59,7 @@ def test_one_rank_equals_the_restatement_bit_for_bit(shape):
     b = ve.run_script(ve.RefAdapter(_dist(1, L, D, **args)), inputs, ve.eval_script())
     for t, (x, y) in enumerate(zip(a, b)):
         for k, v in x["stats"].items():
-            assert np.array_equal(_bits(v), _bits(y["stats"][k])), f"{k} @{t}"
+            assert np.array_equal(bits(v, np.float64), bits(y["stats"][k], np.float64)), f"{k} @{t}"
         for k in ("obs_out", "reward_out", "term_out", "ep_return", "ep_len"):
             if x.get(k) is not None:
                 assert np.array_equal(x[k], y[k], equal_nan=True), f"{k} @{t}"
@@ -95,13 +85,13 @@ def test_combine_ref_is_the_written_fold():
             Ma = Ma + Mb + d * d * na * nb / nt
             ma = ma + d * nb / nt
             na = nt
-        assert _bits(bm[c]) == _bits(ma) and _bits(bv[c]) == _bits(Ma / na), c
+        assert bits(bm[c], np.float64) == bits(ma, np.float64) and bits(bv[c], np.float64) == bits(Ma / na, np.float64), c
     np.testing.assert_allclose(bm, x.mean(axis=0), rtol=1e-13)
     np.testing.assert_allclose(bv, x.var(axis=0), rtol=1e-12)
     # one rank: today's bv = q / n, and a 1-d column is one statistic column
     one = moments_local_ref(x[:L, 0])
     m1, v1, n1 = moments_combine_ref(one[None], L)
-    assert one.shape == (2,) and n1 == L and _bits(m1[0]) == _bits(one[0]) and _bits(v1[0]) == _bits(one[1] / L)
+    assert one.shape == (2,) and n1 == L and bits(m1[0], np.float64) == bits(one[0], np.float64) and bits(v1[0], np.float64) == bits(one[1] / L, np.float64)
     # padded rows (an exchange's stride) are ignored by the caller's slice, and the input is not modified
     before = parts.copy()
     moments_combine_ref(parts, L)
@@ -153,7 +143,7 @@ def test_training_off_moves_nothing():
             assert norm.obs_rms.parts is None and norm.ret_rms.parts is None, "an update ran in evaluation mode"
     for frozen in got[4:7]:
         for k, v in got[3]["stats"].items():
-            assert np.array_equal(_bits(v), _bits(frozen["stats"][k])), k
+            assert np.array_equal(bits(v, np.float64), bits(frozen["stats"][k], np.float64)), k
     assert got[7]["stats"]["ret_count"] == got[3]["stats"]["ret_count"] + 128
     exact = ve.exact_records(("dist-eval",), inputs, ve.DEFAULTS, ve.eval_script())
     w = ve.judge(got, exact, where="dist eval")
@@ -162,14 +152,6 @@ def test_training_off_moves_nothing():
 
 
 # ---- dist.GradExchange(dtype=torch.float64) on two gloo ranks ----------------------------------------------
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
 
 def _payload(rank, n):
     """float64 bit patterns that arithmetic would not keep: NaN payloads, -0.0, subnormals, the extremes."""
@@ -209,20 +191,10 @@ def test_exchange_carries_float64_rows_bit_for_bit():
     """Two gloo ranks: every rank's ``parts`` holds both senders' float64 rows with their bit patterns (NaN
     payloads, -0.0, subnormals), in rank order; the float32 default does the same with float32 blocks."""
     import torch
-    import torch.multiprocessing as mp
 
     from gym_puzzles_amd.dist import GradExchange, Shard
     world, n = 2, 58                  # the part length of 28 obs columns: one stride of 64 with padding
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_exchange_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=240) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    results = spawn(_exchange_worker, world, n)
     assert sorted(r[0] for r in results) == [0, 1]
     for rank, got64, got32 in results:
         assert got64.shape == got32.shape == (2, 64)

@@ -8,18 +8,13 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-
 import vecnorm_exact as ve
+from ppo_cases import bits
 
 pytestmark = pytest.mark.gpu
 
 SENT32 = np.uint32(0x7FC12345)
 SENT64 = np.uint64(0x7FF80000DEADBEEF)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
 
 
 class _Dev:
@@ -88,9 +83,9 @@ def test_world_size_one_equals_the_unsharded_path_bit_for_bit(gpu_lib, shape):
     for t, (x, y) in enumerate(zip(a, b)):
         for k in x:
             if k != "stats":
-                assert np.array_equal(_bits(x[k]), _bits(y[k])), f"{k} @{t}"
+                assert np.array_equal(bits(x[k], None), bits(y[k], None)), f"{k} @{t}"
         for k, v in x["stats"].items():
-            assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(y["stats"][k]))), f"{k} @{t}"
+            assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(y["stats"][k]), None)), f"{k} @{t}"
     assert a[-1]["stats"]["obs_count"] == 1e6 + 2 * L and np.isfinite(parts[0, :2 * (D + 1)]).all()
     assert not parts[0, 2 * (D + 1):].any(), "the local phase wrote past its part"
 
@@ -108,12 +103,12 @@ def test_norm_obs_off_exchanges_the_returns_column_only(gpu_lib):
     shard.norm.exchange.mine.copy_(torch.from_numpy(np.full(64, SENT64).view(np.float64)))
     a = ve.run_script(plain, inputs, ve.plain_script(2))
     b = ve.run_script(shard, inputs, ve.plain_script(2))
-    mine = _bits(shard.norm.exchange.mine.cpu().numpy())
+    mine = bits(shard.norm.exchange.mine.cpu().numpy(), None)
     plain.norm.close(), shard.norm.close()
     assert np.all(mine[:2 * D] == SENT64) and np.all(mine[2 * D:2 * D + 2] != SENT64) and np.all(mine[2 * D + 2:] == SENT64)
     for x, y in zip(a, b):
         for k, v in x["stats"].items():
-            assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(y["stats"][k]))), k
+            assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(y["stats"][k]), None)), k
     assert b[-1]["stats"]["obs_count"] == 1e-4 and b[-1]["stats"]["ret_count"] == (1e-4 + L) + L
 
 
@@ -127,15 +122,15 @@ def test_host_wrapper_passes_the_shard_through(gpu_lib, tmp_path):
     plain, shard = MultiRobotPuzzleVecNormalize(make()), MultiRobotPuzzleVecNormalize(make(), shard=Shard(0, 1, N))
     assert plain.norm.exchange is None and shard.norm.exchange is not None and shard.norm.shard.global_lanes == N
     rs = np.random.RandomState(1)
-    assert np.array_equal(_bits(plain.reset()), _bits(shard.reset()))
+    assert np.array_equal(bits(plain.reset(), None), bits(shard.reset(), None))
     for _ in range(8):
         act = rs.uniform(-1, 1, size=(N, 6)).astype(np.float32)
         (o1, r1, d1, i1), (o2, r2, d2, i2) = plain.step(act), shard.step(act)
-        assert np.array_equal(_bits(o1), _bits(o2)) and np.array_equal(_bits(r1), _bits(r2)) and np.array_equal(d1, d2)
+        assert np.array_equal(bits(o1, None), bits(o2, None)) and np.array_equal(bits(r1, None), bits(r2, None)) and np.array_equal(d1, d2)
         assert [i.get("episode") for i in i1] == [i.get("episode") for i in i2]
     st = shard.get_stats()
     for k, v in plain.get_stats().items():
-        assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(st[k]))), k
+        assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(st[k]), None)), k
     count = 1e-4
     for _ in range(9):                       # the reset and 8 steps, one float64 add each
         count = count + N
@@ -146,7 +141,7 @@ def test_host_wrapper_passes_the_shard_through(gpu_lib, tmp_path):
     back = MultiRobotPuzzleVecNormalize.load(path, make(), shard=Shard(0, 1, N))
     assert back.norm.exchange is not None
     for k, v in st.items():
-        assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(back.get_stats()[k]))), k
+        assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(back.get_stats()[k]), None)), k
     back.close()
 
 

@@ -12,19 +12,14 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-
 import vecnorm_exact as ve
+from ppo_cases import bits
 
 pytestmark = pytest.mark.gpu
 
 SENT32 = np.uint32(0x7FC12345)             # NaN payloads: no kernel arithmetic produces these bits
 SENT64 = np.uint64(0x7FF80000DEADBEEF)
 SENT_LEN = -12345
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
 
 
 class DeviceAdapter:
@@ -67,7 +62,7 @@ class DeviceAdapter:
         out = t_obs if self.in_place else self._sentinel(obs.shape, SENT32)
         self.norm.reset(t_obs, out)
         if not self.in_place:
-            assert np.array_equal(_bits(t_obs.cpu().numpy()), _bits(obs)), "reset changed its input"
+            assert np.array_equal(bits(t_obs.cpu().numpy(), None), bits(obs, None)), "reset changed its input"
         return {"obs_out": out.cpu().numpy(), "stats": self.norm.get_stats()}
 
     def step(self, obs, reward, done, term=None, reward64=None):
@@ -88,18 +83,14 @@ class DeviceAdapter:
         idle = ~np.asarray(done).astype(bool)
         for k, v in ins.items():            # inputs (in place: the ones that are not also outputs)
             if v is not None and not (self.in_place and k in ("obs", "reward", "term")):
-                assert np.array_equal(_bits(host(t[k])), _bits(v)), f"step changed its input {k}"
+                assert np.array_equal(bits(host(t[k]), None), bits(v, None)), f"step changed its input {k}"
         if term is not None:                # rows of lanes that are not done: the sentinel, or in place the input
-            want = _bits(term)[idle] if self.in_place else SENT32
-            assert np.all(_bits(g["term_out"])[idle] == want), "term_out written for a lane that is not done"
+            want = bits(term, None)[idle] if self.in_place else SENT32
+            assert np.all(bits(g["term_out"], None)[idle] == want), "term_out written for a lane that is not done"
         if self.monitor:
-            assert np.all(_bits(g["ep_return"])[idle] == SENT64), "ep_return written for a lane that is not done"
+            assert np.all(bits(g["ep_return"], None)[idle] == SENT64), "ep_return written for a lane that is not done"
             assert np.all(g["ep_len"][idle] == SENT_LEN), "ep_len written for a lane that is not done"
         return g
-
-
-def _clips(args):
-    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
 
 
 def _show(name, worst):
@@ -115,7 +106,7 @@ def test_statistics_and_outputs_against_exact(gpu_lib, i):
     dev = DeviceAdapter(L, D, **args)
     got = ve.run_script(dev, inputs, ve.plain_script())
     dev.close()
-    _show(ve.case_id(ve.CASES[i]), ve.judge(got, ve.exact_case(i), *_clips(args), where=ve.case_id(ve.CASES[i])))
+    _show(ve.case_id(ve.CASES[i]), ve.judge(got, ve.exact_case(i), *ve.clips(args), where=ve.case_id(ve.CASES[i])))
     assert sum(int(s["done"].sum()) for s in inputs["steps"]) >= L     # Monitor and term_out were exercised
 
 
@@ -129,10 +120,10 @@ def test_evaluation_mode_freezes_everything_but_monitor(gpu_lib):
     dev = DeviceAdapter(inputs["L"], inputs["D"], **args)
     got = ve.run_script(dev, inputs, script)
     dev.close()
-    _show("eval", ve.judge(got, ve.exact_scenario("eval"), *_clips(args), where="eval"))
+    _show("eval", ve.judge(got, ve.exact_scenario("eval"), *ve.clips(args), where="eval"))
     for frozen in got[4:7]:          # calls: reset, steps 0-2 (training), 3-5 (frozen), 6-7 (training)
         for k, v in got[3]["stats"].items():
-            assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(frozen["stats"][k]))), k
+            assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(frozen["stats"][k]), None)), k
     assert got[7]["stats"]["ret_count"] == got[3]["stats"]["ret_count"] + inputs["L"]
     done_while_frozen = sum(int(inputs["steps"][k]["done"].sum()) for k in range(3, 6))
     assert done_while_frozen > 0 and any(int(g["ep_len"][inputs["steps"][k]["done"].astype(bool)].max()) > 1
@@ -166,7 +157,7 @@ def test_set_stats_then_step(gpu_lib):
     got = ve.run_script(dev, inputs, script)
     dev.close()
     exact = ve.exact_scenario("set_stats")
-    _show("set_stats", ve.judge(got, exact, *_clips(args), where="set_stats"))
+    _show("set_stats", ve.judge(got, exact, *ve.clips(args), where="set_stats"))
     first = exact[1]                                                     # the step after the load
     moved = np.abs(np.asarray(first["stats"]["obs_mean"], np.float64) - loaded["obs_mean"])
     assert np.all(moved > first["stat_bounds"]["obs_mean"]), (moved, first["stat_bounds"]["obs_mean"])
@@ -182,7 +173,7 @@ def test_reset_mid_run(gpu_lib):
     got = ve.run_script(dev, inputs, script)
     dev.close()
     exact = ve.exact_scenario("reset")
-    _show("reset", ve.judge(got, exact, *_clips(args), where="reset"))
+    _show("reset", ve.judge(got, exact, *ve.clips(args), where="reset"))
     L = inputs["L"]
     assert got[4]["stats"]["obs_count"] == got[3]["stats"]["obs_count"] + L          # the second reset counted
     assert got[4]["stats"]["ret_count"] == got[3]["stats"]["ret_count"]
@@ -205,11 +196,11 @@ def test_in_place_outputs(gpu_lib):
         m = ve.case_inputs(i)["steps"][t - 1]["done"].astype(bool) if t else None
         for k in ("obs_out", "reward_out", "ep_return", "ep_len"):
             if x.get(k) is not None:
-                assert np.array_equal(_bits(x[k]), _bits(y[k])), f"{k} @{t}"
+                assert np.array_equal(bits(x[k], None), bits(y[k], None)), f"{k} @{t}"
         if t:
-            assert np.array_equal(_bits(x["term_out"])[m], _bits(y["term_out"])[m]), f"term_out @{t}"
+            assert np.array_equal(bits(x["term_out"], None)[m], bits(y["term_out"], None)[m]), f"term_out @{t}"
         for k, v in x["stats"].items():
-            assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(y["stats"][k]))), f"{k} @{t}"
+            assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(y["stats"][k]), None)), f"{k} @{t}"
 
 
 def test_optional_outputs_absent(gpu_lib):
@@ -236,9 +227,9 @@ def test_optional_outputs_absent(gpu_lib):
             for k in keys:
                 if full.get(k) is not None:
                     sel = slice(None) if k in ("obs_out", "reward_out") else m
-                    assert np.array_equal(_bits(full[k])[sel], _bits(g[k])[sel]), f"{what}: {k} @{t}"
+                    assert np.array_equal(bits(full[k], None)[sel], bits(g[k], None)[sel]), f"{what}: {k} @{t}"
             for k, v in full["stats"].items():
-                assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(g["stats"][k]))), f"{what}: {k} @{t}"
+                assert np.array_equal(bits(np.asarray(v), None), bits(np.asarray(g["stats"][k]), None)), f"{what}: {k} @{t}"
         if t:
             assert runs["no term"][t]["term_out"] is None and runs["no monitor"][t]["ep_return"] is None
             acc = acc + inputs["steps"][t - 1]["reward"].astype(np.float64)
@@ -301,10 +292,10 @@ def test_nonfinite_inputs_follow_numpy(gpu_lib):
     g = ve.run_script(dev, inputs, script)[-1]
     dev.close()
     r = ve.run_script(ve.RefAdapter(VecNormalizeRef(65, 3)), inputs, script)[-1]
-    ten = _bits(np.array([10.0, -10.0], np.float32))
-    assert _bits(g["obs_out"])[3, 0] == ten[0] and _bits(g["obs_out"])[64, 2] == ten[1] and np.isnan(g["obs_out"][9, 1])
-    assert _bits(g["term_out"])[5, 0] == ten[0]
-    assert _bits(g["reward_out"])[0] == ten[0] and _bits(g["reward_out"])[64] == ten[1] and np.isnan(g["reward_out"][7])
+    ten = bits(np.array([10.0, -10.0], np.float32), None)
+    assert bits(g["obs_out"], None)[3, 0] == ten[0] and bits(g["obs_out"], None)[64, 2] == ten[1] and np.isnan(g["obs_out"][9, 1])
+    assert bits(g["term_out"], None)[5, 0] == ten[0]
+    assert bits(g["reward_out"], None)[0] == ten[0] and bits(g["reward_out"], None)[64] == ten[1] and np.isnan(g["reward_out"][7])
     for k, n_nan in (("obs_out", 1), ("term_out", 0), ("reward_out", 1)):
         assert np.array_equal(np.isnan(g[k]), np.isnan(r[k])) and int(np.isnan(g[k]).sum()) == n_nan, k
         np.testing.assert_allclose(g[k], r[k], rtol=1e-6, atol=1e-6, err_msg=k)

@@ -9,33 +9,12 @@ tests check the same claim end to end: trajectories bitwise equal to the oracle.
 """
 from __future__ import annotations
 
-import os
-import shutil
-import subprocess
-
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _hipcc():
-    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
+import hostprog
 
 
 def test_packed_pair_identities(tmp_path):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    exe = tmp_path / "packed_check"
-    from gym_puzzles_amd.build import FLAGS
     # the library's numerics flags, host side only (no device code in the check)
-    flags = [f for f in FLAGS if not f.startswith("--offload-arch") and f != "-fPIC"]
-    subprocess.run([hipcc, *flags, "-x", "hip", "--cuda-host-only", os.path.join(HERE, "packed_check.cpp"), "-o", str(exe)],
-                   check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostprog.run(hostprog.build("packed_check.cpp", tmp_path / "packed_check", hostprog.library_flags()))
     lines = dict((ln.split()[0], (int(ln.split()[1]), int(ln.split()[2]))) for ln in r.stdout.strip().splitlines())
     assert set(lines) == {"cross_sv", "cross", "cross_from_perp", "dot", "mul_rv", "tangent", "v_minus_mP", "v_plus_mP"}
     for name, (bad, n) in lines.items():

@@ -3,20 +3,18 @@ tanh rule, the linear layer and the distribution against float64, the SB3 state_
 the argument limits.  No device is used here; tests/test_policy_gpu.py pins the kernel to the rule."""
 from __future__ import annotations
 
+import hashlib
 import math
 from fractions import Fraction
 
 import numpy as np
 import pytest
+from ppo_cases import ARCHS, bits, make_batch, make_params
 
 from gym_puzzles_amd import policy as P
 
 U = 2.0 ** -24          # float32 unit roundoff
 TANH_ULPS = 0.501       # measured maximum of tanh_ref (DESIGN.md "Device policy"): 0.5 ulp + 2^-25, asserted below
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # ---- the fma scheme ----------------------------------------------------------------------------------
@@ -70,9 +68,9 @@ def test_fma_scheme_is_an_fma():
         want = np.array([np.float32(math.fma(float(x), float(y), float(z))) for x, y, z in zip(a, b, c)], np.float32)
     else:
         want = np.array([_fma_exact(x, y, z) for x, y, z in zip(a, b, c)], np.float32)
-    assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(bits(got), bits(want))
     naive = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-    assert not np.array_equal(_bits(naive), _bits(want)), "the triples include cases where double rounding shows"
+    assert not np.array_equal(bits(naive), bits(want)), "the triples include cases where double rounding shows"
 
 
 # ---- tanh --------------------------------------------------------------------------------------------
@@ -103,14 +101,14 @@ def _ulps(got32, x32):
 def test_tanh_properties():
     x = np.sort(np.concatenate([np.linspace(-21, 21, 400_001), np.linspace(-0.01, 0.01, 200_001)]).astype(np.float32))
     t = P.tanh_ref(x)
-    assert np.array_equal(_bits(P.tanh_ref(-x)), _bits(-t)), "odd"
+    assert np.array_equal(bits(P.tanh_ref(-x)), bits(-t)), "odd"
     assert (np.diff(t) >= 0).all(), "monotone"
     assert (np.abs(t) <= 1).all() and (t[x >= 9.5] == 1).all() and (t[x <= -9.5] == -1).all()
     sp = np.array([0.0, -0.0, np.inf, -np.inf, 1e30, -1e30, 20.0, np.float32(20.0) - np.spacing(np.float32(19.0))], np.float32)
     want = np.array([0.0, -0.0, 1.0, -1.0, 1.0, -1.0, 1.0, 1.0], np.float32)
-    assert np.array_equal(_bits(P.tanh_ref(sp)), _bits(want))
+    assert np.array_equal(bits(P.tanh_ref(sp)), bits(want))
     nans = np.array([0x7FC00000, 0xFFC00001, 0x7F800001, 0xFFFFFFFF], np.uint32).view(np.float32)
-    assert np.array_equal(_bits(P.tanh_ref(nans)), _bits(nans)), "NaN comes back unchanged"
+    assert np.array_equal(bits(P.tanh_ref(nans)), bits(nans)), "NaN comes back unchanged"
 
 
 def test_tanh_accuracy():
@@ -136,7 +134,7 @@ def test_linear_layer_against_float64():
     # (products of -0 leave a bias of -0 alone, one product of +0 turns it into +0)
     w = np.array([[-1, -1, -1], [-1, 1, -1]], np.float32)
     z = P.linear_ref(np.zeros((1, 3), np.float32), w, np.array([-0.0, -0.0], np.float32))
-    assert np.array_equal(_bits(z), _bits(np.array([[-0.0, 0.0]], np.float32)))
+    assert np.array_equal(bits(z), bits(np.array([[-0.0, 0.0]], np.float32)))
 
 
 def _sb3_tree(obs_dim, act_dim, shared, pi, vf, activation, seed):
@@ -219,7 +217,7 @@ def test_loader_and_forward_against_the_torch_tree(arch):
     assert em.max() < 1e-3 and ev.max() < 1e-3, "the bound itself stays far below a transposed weight's O(1) error"
     assert (np.abs(actions.astype(np.float64) - tm.numpy()) <= em).all()
     assert (np.abs(values.astype(np.float64) - tv.numpy()) <= ev).all()
-    assert np.array_equal(_bits(P.values_ref(params, obs)), _bits(values))
+    assert np.array_equal(bits(P.values_ref(params, obs)), bits(values))
 
 
 def test_log_prob_and_clipped_against_float64():
@@ -277,3 +275,49 @@ def test_argument_errors():
             case()
     P.check_arch(256, 16, 2, 2, 2, [256] * 6)
     P.check_arch(1, 1, 0, 1, 0, [1])
+
+
+# ---- the synthetic network ---------------------------------------------------------------------------
+# sha256 over flatten_params(...) and log_std, in turn, of the parameters that the tests, the benches and the
+# data-parallel worker run on.  Every bitwise test compares device and rule on the same parameters, so a drifted
+# generator would pass them all while changing which cases are covered.
+PINNED = {
+    # ppo_cases.make_params at seeds 0, 3, 4 and at seed 4 with negzero_bias
+    "sb3-default": "e4181dedf47859f053e6bc833b7e7ea3c62d5a06fc884577e2c9f9eddbadd15a",
+    "reference-config": "49108dbbb7e2af362e434b7278a315f8a47021c0f373484b0cb170190ba754c3",
+    "odd-k-wide-head": "844e6b201f2cc4243f248dff417e8e2e6ceb647a5effe5ba9338fe3605c47444",
+    "heads-only": "9ecaba34bc4ce0082d9ec46512833e966938c9939754163f41f72a20838fc236",
+    "one-by-one": "7a4676670171c297c1103961b88411924df2d187e7cce58e3b9b4bd09b635b0c",
+    "width-one-inside": "42f9bd4a92c275783a2c4907a59c7da3413565e0c37fc91b8795912dd6fa7fd4",
+    "width-one-towers": "52ace16eb62929dac105b45ec1a0212a30cc871bd36f88e946c336a5d173227e",
+    # the benches' two architectures (tools/trainbench.py bench_params) at seed len(name)
+    "sb3_default_pi64x2_vf64x2": "d154e36d20b3c8c739c33d52551f9f999e0b8b836a69844c28ecaa49996020cb",
+    "reference_shared256x2": "3aabc5f86607d61cf4d2a96fcd5da9e5ba8d5b5801d9e1071ea5da195f88b663",
+    # tools/ppo_ddp_worker.py's ranks 0 and 1
+    "ddp-worker-seed-10": "477e9123b652a5ddc6bee1ae208d10afb28f89b2336c8c567502d7fb31dabc97",
+    "ddp-worker-seed-11": "75d4f81f8d07a77a3b8ff4c96817765287ae8b173c3c54ff837da3a708f8940c",
+    # the five arrays of make_batch(make_params(sb3-default, seed 3), 33)
+    "make_batch": "e29bfd0e658bd0feccca5ec412c510e540053899f87d032a3edbec85e1717055",
+}
+
+
+def test_random_params_are_pinned():
+    def digest(arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        return h.hexdigest()
+    of = lambda params: [P.flatten_params(params), params.log_std]  # noqa: E731
+    got = {}
+    for name, arch in ARCHS.items():
+        runs = [make_params(arch, seed) for seed in (0, 3, 4)] + [make_params(arch, 4, negzero_bias=True)]
+        got[name] = digest([a for params in runs for a in of(params)])
+    bench_log_std = np.linspace(-0.5, 0.0, 6).astype(np.float32)
+    for name, shared, pi, vf in (("sb3_default_pi64x2_vf64x2", [], [64, 64], [64, 64]), ("reference_shared256x2", [256, 256], [], [])):
+        got[name] = digest(of(P.random_params(28, 6, shared, pi, vf, "tanh", len(name), 0.1, bench_log_std)))
+    for seed in (10, 11):
+        got[f"ddp-worker-seed-{seed}"] = digest(of(P.random_params(28, 6, [], [64, 64], [64, 64], "tanh", seed, 0.1, bench_log_std)))
+    got["make_batch"] = digest(make_batch(make_params(ARCHS["sb3-default"], seed=3), 33))
+    assert got == PINNED
+    zero = make_params(ARCHS["odd-k-wide-head"], 4, negzero_bias=True)
+    assert all((w < 0).all() and np.signbit(b).all() and not b.any() for w, b in P._layers(zero))

@@ -4,56 +4,15 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from ppo_cases import ARCHS, make_params, same
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd.rollout import gae_ref
 
 pytestmark = pytest.mark.gpu
 
+NAMES = ("sb3-default", "reference-config", "odd-k-wide-head", "heads-only", "one-by-one")
 LANES = (1, 31, 33, 65, 130)      # partial tiles, a second workgroup, a partial tile in a later workgroup
-# obs, act, (S, P, V), widths (trunk, policy tower, value tower), activation
-ARCHS = {
-    "sb3-default": (28, 6, (0, 2, 2), [64, 64, 64, 64], "tanh"),
-    "reference-config": (28, 6, (2, 0, 0), [256, 256], "tanh"),
-    "odd-k-wide-head": (27, 15, (1, 1, 1), [40, 24, 8], "relu"),
-    "heads-only": (69, 4, (0, 0, 0), [], "tanh"),
-    "one-by-one": (1, 1, (0, 1, 0), [1], "relu"),
-}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    bad = np.flatnonzero(_bits(got).ravel() != _bits(want).ravel())
-    assert bad.size == 0, f"{what}: {bad.size} of {want.size} differ, first at {bad[:5]}: {got.ravel()[bad[:5]]} != {want.ravel()[bad[:5]]}"
-
-
-def _params(name, seed=0, negzero_bias=False):
-    obs_dim, act_dim, (S, Pn, V), widths, activation = ARCHS[name]
-    rng = np.random.default_rng(seed)
-
-    def lin(k, n):
-        w = (rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32)
-        b = (rng.standard_normal(n) * 0.3).astype(np.float32)
-        if negzero_bias:        # all weights negative: a row of +0 makes products of -0, which leave a bias of -0 alone
-            w, b = -np.abs(w), np.full(n, -0.0, np.float32)
-        return w, b
-
-    def tower(k, ws):
-        out = []
-        for n in ws:
-            out.append(lin(k, n))
-            k = n
-        return out, k
-    shared, kt = tower(obs_dim, widths[:S])
-    pi, kp = tower(kt, widths[S:S + Pn])
-    vf, kv = tower(kt, widths[S + Pn:])
-    log_std = np.linspace(-0.8, 0.2, act_dim).astype(np.float32)
-    return P.PolicyParams(shared, pi, vf, lin(kp, act_dim), lin(kv, 1), log_std, activation)
-
 
 _CACHE = {}
 
@@ -61,7 +20,7 @@ _CACHE = {}
 def _case(name):
     """(params, obs for max(LANES), eps, reference outputs): computed once per architecture, never changed."""
     if name not in _CACHE:
-        params = _params(name)
+        params = make_params(ARCHS[name])
         rng = np.random.default_rng(17)
         N = max(LANES)
         obs = rng.standard_normal((N, params.obs_dim)).astype(np.float32)
@@ -70,7 +29,7 @@ def _case(name):
     return _CACHE[name]
 
 
-@pytest.mark.parametrize("name", list(ARCHS))
+@pytest.mark.parametrize("name", NAMES)
 def test_bitwise_forward(gpu_lib, name):
     import torch
     params, obs, eps, want = _case(name)
@@ -78,7 +37,7 @@ def test_bitwise_forward(gpu_lib, name):
     for N in LANES:
         got = pol.act(torch.from_numpy(obs[:N]).cuda(), eps=torch.from_numpy(eps[:N]).cuda())
         for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
-            _same(g, w[:N], f"{name} N={N} {what}")
+            same(g, w[:N], f"{name} N={N} {what}")
     assert pol.counter == 0, "host-supplied noise leaves the counter alone"
     pol.close()
 
@@ -89,7 +48,7 @@ def test_zeros_and_negative_zeros(gpu_lib, name):
     are zeros of one sign, so the outputs are zeros whose sign alternates with the depth, and a pad term
     fma(0, 0, acc) anywhere in a chain would turn a -0 into +0."""
     import torch
-    params = _params(name, seed=4, negzero_bias=True)
+    params = make_params(ARCHS[name], seed=4, negzero_bias=True)
     obs = np.random.default_rng(1).standard_normal((40, params.obs_dim)).astype(np.float32)
     obs[3] = 0.0
     obs[36] = -0.0
@@ -101,7 +60,7 @@ def test_zeros_and_negative_zeros(gpu_lib, name):
     pol = P.DevicePolicy.from_params(params)
     got = pol.act(torch.from_numpy(obs).cuda(), eps=torch.from_numpy(eps).cuda())
     for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
-        _same(g, w, f"{name} {what}")
+        same(g, w, f"{name} {what}")
     pol.close()
 
 
@@ -112,14 +71,14 @@ def test_values_only_and_deterministic(gpu_lib, name):
     pol = P.DevicePolicy.from_params(params)
     d_obs = torch.from_numpy(obs).cuda()
     a, c, v, lp = pol.act(d_obs, eps=torch.from_numpy(eps).cuda())
-    _same(pol.values(d_obs), v.cpu().numpy(), "values() against act's values")
-    _same(pol.values(d_obs[:33].contiguous()), want[2][:33], "values() against the rule")
+    same(pol.values(d_obs), v.cpu().numpy(), "values() against act's values")
+    same(pol.values(d_obs[:33].contiguous()), want[2][:33], "values() against the rule")
     det = pol.act(d_obs, deterministic=True)
     wdet = P.policy_ref(params, obs, deterministic=True)
     for g, w, what in zip(det, wdet, ("actions", "clipped", "values", "log_probs")):
-        _same(g, w, f"deterministic {what}")
+        same(g, w, f"deterministic {what}")
     mean = P.linear_ref(P.features_ref(params, obs, "pi"), *params.action)
-    _same(det[0], mean, "deterministic actions are the mean")
+    same(det[0], mean, "deterministic actions are the mean")
     assert pol.counter == 0
     pol.close()
 
@@ -145,12 +104,12 @@ def test_tanh_on_the_device(gpu_lib):
     out = np.zeros_like(x)
     rc = gpu_lib.mrp_selftest_tanh(0, _native._p(x), _native._p(out), x.size)
     assert rc == 0
-    _same(out, P.tanh_ref(x), "tanh_f32 on the device against tanh_ref")
+    same(out, P.tanh_ref(x), "tanh_f32 on the device against tanh_ref")
 
 
 def test_device_rng(gpu_lib):
     import torch
-    params = _params("odd-k-wide-head", seed=2)
+    params = make_params(ARCHS["odd-k-wide-head"], seed=2)
     N, A = 256, params.act_dim
     obs = np.random.default_rng(3).standard_normal((N, params.obs_dim)).astype(np.float32)
     d_obs = torch.from_numpy(obs).cuda()
@@ -161,7 +120,7 @@ def test_device_rng(gpu_lib):
     assert pol.counter == 1
     # the outputs are the rule applied to the emitted noise
     for g, w, what in zip(out0, P.policy_ref(params, obs, e0.cpu().numpy()), ("actions", "clipped", "values", "log_probs")):
-        _same(g, w, f"device noise: {what}")
+        same(g, w, f"device noise: {what}")
     # lanes are keyed by lane_offset + lane: two half batches make the whole
     halves = []
     for off in (0, N // 2):
@@ -172,12 +131,12 @@ def test_device_rng(gpu_lib):
         half.close()
     for i, what in enumerate(("actions", "clipped", "values", "log_probs", "eps")):
         whole = out0[i] if i < 4 else e0.cpu().numpy()
-        _same(np.concatenate([halves[0][i], halves[1][i]]), whole, f"half batches: {what}")
+        same(np.concatenate([halves[0][i], halves[1][i]]), whole, f"half batches: {what}")
     # the same counter repeats, the next one differs
     pol.counter = 0
     e0b = z(N, A)
     pol.act(d_obs, eps_out=e0b)
-    _same(e0b, e0.cpu().numpy(), "the same counter")
+    same(e0b, e0.cpu().numpy(), "the same counter")
     e1 = z(N, A)
     pol.act(d_obs, eps_out=e1)
     assert pol.counter == 2 and not np.array_equal(e1.cpu().numpy(), e0.cpu().numpy())
@@ -216,10 +175,10 @@ def test_inputs_are_not_written_and_outputs_are_the_callers(gpu_lib):
     assert all(g is o for g, o in zip(got, out))
     vout = z(N)
     assert pol.values(d_obs, out=vout) is vout
-    _same(d_obs, obs[:N], "obs after the launches")
-    _same(d_eps, eps[:N], "eps after the launches")
-    _same(out[3], want[3][:N], "log_probs")
-    _same(vout, want[2][:N], "values")
+    same(d_obs, obs[:N], "obs after the launches")
+    same(d_eps, eps[:N], "eps after the launches")
+    same(out[3], want[3][:N], "log_probs")
+    same(vout, want[2][:N], "values")
     pol.close()
 
 
@@ -261,7 +220,7 @@ def test_argument_errors(gpu_lib):
     with pytest.raises(ValueError):
         empty.set_params(_case("reference-config")[0])
     empty.set_params(params)
-    _same(empty.values(d_obs), _case("sb3-default")[3][2][:N], "values after set_params")
+    same(empty.values(d_obs), _case("sb3-default")[3][2][:N], "values after set_params")
     with pytest.raises(ValueError):
         P.DevicePolicy(28, 17, 0, 0, 0, [])
     with pytest.raises(ValueError):
@@ -286,10 +245,10 @@ def test_outputs_may_touch_an_input_but_not_overlap_it(gpu_lib):
     z = lambda *s: torch.zeros(s, dtype=torch.float32, device="cuda")  # noqa: E731
     with pytest.raises(ValueError, match="alias"):
         pol.act(d_obs, eps=d_eps, out=(big[N * O - 6:N * O - 6 + N * A].view(N, A), z(N, A), z(N), z(N)))
-    _same(d_obs, obs[:N], "a refused call wrote nothing")
+    same(d_obs, obs[:N], "a refused call wrote nothing")
     got = pol.act(d_obs, eps=d_eps, out=(big[N * O:].view(N, A), z(N, A), z(N), z(N)))
     for g, w, what in zip(got, want, ("actions", "clipped", "values", "log_probs")):
-        _same(g, w.cpu().numpy(), f"actions behind obs: {what}")
+        same(g, w.cpu().numpy(), f"actions behind obs: {what}")
     pol.close()
 
 
@@ -305,7 +264,7 @@ def test_collect_rollouts_end_to_end(gpu_lib, with_norm):
     dev = torch.device("cuda", 0)
     env = MultiRobotPuzzleVecEnv("MultiRobotPuzzle-v0", N, seed=3, max_episode_steps=5)
     O, A = env.observation_space.shape[0], env.action_space.shape[0]
-    params = _params("sb3-default", seed=6)
+    params = make_params(ARCHS["sb3-default"], seed=6)
     assert (params.obs_dim, params.act_dim) == (O, A)
     pol = P.DevicePolicy.from_params(params, seed=77)
     buf = DeviceRolloutBuffer(T, N, (O,), A, device=0, gamma=0.99, gae_lambda=0.95)
@@ -321,7 +280,7 @@ def test_collect_rollouts_end_to_end(gpu_lib, with_norm):
     obs_in, start_in = obs0.clone(), start0.clone()
     nxt_obs, nxt_start = collect_rollouts(env, pol, buf, obs0, start0, norm=norm, eps_out=eps)
     assert buf.full and pol.counter == T
-    _same(obs0, obs_in.cpu().numpy(), "the caller's obs")
+    same(obs0, obs_in.cpu().numpy(), "the caller's obs")
     assert torch.equal(start0, start_in)
     h = lambda t: t.cpu().numpy()  # noqa: E731
     b_obs, b_act, b_val, b_lp, h_eps = h(buf.observations), h(buf.actions), h(buf.values), h(buf.log_probs), h(eps)
@@ -338,29 +297,29 @@ def test_collect_rollouts_end_to_end(gpu_lib, with_norm):
     assert (np.abs(b_act) > 1).any(), "some stored actions lie outside the box, so clipping is visible"
     n_trunc = 0
     for t in range(T):
-        _same(cur, b_obs[t], f"row {t}: the replayed env's observations (it was stepped with the clipped actions)")
+        same(cur, b_obs[t], f"row {t}: the replayed env's observations (it was stepped with the clipped actions)")
         want = P.policy_ref(params, b_obs[t], h_eps[t])
-        _same(b_act[t], want[0], f"row {t}: the stored actions are the unclipped ones")
-        _same(b_val[t], want[2], f"row {t}: values")
-        _same(b_lp[t], want[3], f"row {t}: log_probs")
+        same(b_act[t], want[0], f"row {t}: the stored actions are the unclipped ones")
+        same(b_val[t], want[2], f"row {t}: values")
+        same(b_lp[t], want[3], f"row {t}: log_probs")
         env2.step_torch(torch.from_numpy(want[1]).to(dev), nraw, rew, done, truncated=trunc, terminal_obs=term)
         if norm2 is not None:
             norm2.step(nraw, rew, done, nobs, nrew, term_obs=term, term_out=nterm)
-        _same(buf.rewards[t], h(nrew), f"row {t}: rewards")
-        _same(buf.truncated[t].to(torch.float32), h(trunc).astype(np.float32), f"row {t}: truncated")
+        same(buf.rewards[t], h(nrew), f"row {t}: rewards")
+        same(buf.truncated[t].to(torch.float32), h(trunc).astype(np.float32), f"row {t}: truncated")
         m = h(trunc).astype(bool)
         if m.any():
             n_trunc += int(m.sum())
-            _same(h(buf.terminal_values[t])[m], P.values_ref(params, h(nterm)[m]), f"row {t}: terminal values")
+            same(h(buf.terminal_values[t])[m], P.values_ref(params, h(nterm)[m]), f"row {t}: terminal values")
         cur = nobs.clone()
     assert n_trunc >= 64
-    _same(nxt_obs, h(cur), "the returned observations")
+    same(nxt_obs, h(cur), "the returned observations")
     assert torch.equal(nxt_start, done)
     last_values = P.values_ref(params, h(cur))
     want_a, want_r = gae_ref(h(buf.rewards), b_val, h(buf.episode_starts).astype(np.float32), last_values, h(done), 0.99, 0.95,
                              h(buf.truncated), h(buf.terminal_values))
-    _same(buf.advantages, want_a, "advantages")
-    _same(buf.returns, want_r, "returns")
+    same(buf.advantages, want_a, "advantages")
+    same(buf.returns, want_r, "returns")
     assert h(buf.episode_starts)[0].all()
     for x in (env, env2, pol) + ((norm, norm2) if with_norm else ()):
         x.close()

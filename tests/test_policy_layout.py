@@ -3,38 +3,27 @@
 mrp_policy_set_params scatters the flat parameter vector through this map into the device image,
 mrp_policy_get_params gathers it back and mrp_ppo_create takes its index tables from it, so it is the
 one place where a padding or stride mistake can be made.  tests/policy_layout_check.cpp walks the map
-for each architecture of tests/test_ppo_gpu.py (the two width-one ones and one-by-one are the smallest
+for each architecture of tests/ppo_cases.py (the two width-one ones and one-by-one are the smallest
 at which such a mistake shows); it is a stand-alone program built host-only with the address and
 undefined-behaviour sanitizers.  Here the map is compared with a numpy restatement of the image layout
 and with the flat order of gym_puzzles_amd.policy.flatten_params.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
+import hostprog
 import numpy as np
 import pytest
-from test_packed import _hipcc
-from test_ppo import make_params
-from test_ppo_gpu import ARCHS
+from ppo_cases import ARCHS, make_params
 
 from gym_puzzles_amd import policy as P
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("policy_layout") / "policy_layout_check"
     # the sanitizers instrument the host code only (-Xarch_host): no device code is built, let alone sanitized
-    subprocess.run([hipcc, "-std=c++17", "-O1", "-g", "-x", "hip", "--cuda-host-only", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", os.path.join(HERE, "policy_layout_check.cpp"), "-o", str(out)],
-                   check=True, capture_output=True)
-    return str(out)
+    return hostprog.build("policy_layout_check.cpp", tmp_path_factory.mktemp("policy_layout") / "policy_layout_check",
+                          ["-std=c++17", "-O1", "-g"],
+                          ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"])
 
 
 def _up(n, m):
@@ -81,7 +70,7 @@ def image_ref(arch):
 def test_parameter_map(exe, name):
     arch = ARCHS[name]
     obs_dim, act_dim, (S, Pn, V), widths, _ = arch
-    r = subprocess.run([exe, *map(str, (obs_dim, act_dim, S, Pn, V, *widths))], capture_output=True, text=True)
+    r = hostprog.run(exe, *map(str, (obs_dim, act_dim, S, Pn, V, *widths)))
     assert r.returncode == 0, r.stderr[-2000:]
     rows = np.array(r.stdout.split(), np.int64)
     n_floats, n_params = rows[:2]

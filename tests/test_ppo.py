@@ -7,83 +7,16 @@ import math
 
 import numpy as np
 import pytest
+from ppo_cases import ARCHS, BATCHES, WRONG, U, exp_inputs, majorant, make_batch, make_params, sb3_loss, torch_policy
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd import ppo as R
 
-U = 2.0 ** -24          # unit roundoff of float32
 EXP_ULPS = 0.501
-
-# obs, act, (S, P, V), widths, activation: three of tests/test_policy_gpu.py's ARCHS
-ARCHS = {
-    "sb3-default": (28, 6, (0, 2, 2), [64, 64, 64, 64], "tanh"),
-    "odd-k-wide-head": (27, 15, (1, 1, 1), [40, 24, 8], "relu"),
-    "heads-only": (69, 4, (0, 0, 0), [], "tanh"),
-}
-BATCHES = (1, 33, 300)
-
-
-def make_params(arch, seed=0, negzero_bias=False):
-    obs_dim, act_dim, (S, Pn, V), widths, activation = arch
-    rng = np.random.default_rng(seed)
-
-    def lin(k, n):
-        w = (rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32)
-        b = (rng.standard_normal(n) * 0.3).astype(np.float32)
-        if negzero_bias:
-            w, b = -np.abs(w), np.full(n, -0.0, np.float32)
-        return w, b
-
-    def tower(k, ws):
-        out = []
-        for n in ws:
-            out.append(lin(k, n))
-            k = n
-        return out, k
-    shared, kt = tower(obs_dim, widths[:S])
-    pi, kp = tower(kt, widths[S:S + Pn])
-    vf, kv = tower(kt, widths[S + Pn:])
-    log_std = np.linspace(-0.8, 0.2, act_dim).astype(np.float32)
-    return P.PolicyParams(shared, pi, vf, lin(kp, act_dim), lin(kv, 1), log_std, activation)
-
-
-def make_batch(params, B, seed=5, clip=0.2):
-    """A minibatch whose ratios fall inside (case 0), above (1) and below (2) the clip range, each with
-    both advantage signs when B allows: sample n is case n % 3 with the sign of (n // 3) % 2."""
-    rng = np.random.default_rng(seed)
-    obs = rng.standard_normal((B, params.obs_dim)).astype(np.float32)
-    eps = rng.standard_normal((B, params.act_dim)).astype(np.float32)
-    actions, _, values, lp = P.policy_ref(params, obs, eps)
-    n = np.arange(B)
-    case, sign = n % 3, np.where((n // 3) % 2 == 0, 1.0, -1.0)
-    offs = np.where(case == 0, rng.uniform(-0.1, 0.1, B), np.where(case == 1, 0.4, -0.4)) + rng.uniform(-0.02, 0.02, B)
-    old = (lp.astype(np.float64) - offs).astype(np.float32)          # ratio = exp(offs)
-    adv = (sign * rng.uniform(0.2, 2.0, B)).astype(np.float32)
-    ret = (values + rng.standard_normal(B)).astype(np.float32)
-    return obs, actions, old, adv, ret
+NAMES = ("sb3-default", "odd-k-wide-head", "heads-only")
 
 
 # ---- exp ---------------------------------------------------------------------------------------------
-def exp_inputs():
-    rng = np.random.default_rng(11)
-    sweep = np.linspace(-104, 89, 200_001).astype(np.float32)
-    near = []
-    for n in range(-151, 130):              # where n = nearest(x / ln 2) steps
-        b = int(np.float32(abs((n + 0.5) * math.log(2.0))).view(np.uint32))
-        a = np.arange(b - 2000, b + 2001, dtype=np.uint32).view(np.float32)
-        near.append(a if n + 0.5 > 0 else -a)
-    thresholds = []
-    for x in (88.72284, -87.33655, -103.27893, -103.97208, 89.0, -104.0):   # overflow, subnormal, underflow, the clamps
-        b = int(np.float32(abs(x)).view(np.uint32))
-        a = np.arange(b - 2000, b + 2001, dtype=np.uint32).view(np.float32)
-        thresholds.append(a if x > 0 else -a)
-    subn = rng.uniform(-103.9, -87.4, 20_000).astype(np.float32)
-    special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e-45, -1e-45, 1e-10, -1e-10, 200.0, -200.0, 3e38, -3e38], np.float32)
-    special = np.concatenate([special, np.array([0x7F800001, 0xFFC00123, 0x7FC00000, 0xFF800001], np.uint32).view(np.float32)])
-    rand = rng.integers(0, 1 << 32, 50_000, dtype=np.uint64).astype(np.uint32).view(np.float32)
-    return sweep, np.concatenate([sweep, np.concatenate(near), np.concatenate(thresholds), subn, special, rand])
-
-
 def test_exp_ref_accuracy_and_monotone():
     sweep, x = exp_inputs()
     got = R.exp_ref(x)
@@ -107,141 +40,6 @@ def test_exp_ref_accuracy_and_monotone():
 
 
 # ---- the rule is PPO ---------------------------------------------------------------------------------
-def torch_policy(params):
-    """The network as a float64 torch module tree under SB3's parameter names."""
-    import torch
-    from torch import nn
-    act = nn.Tanh if params.activation == "tanh" else nn.ReLU
-
-    def seq(layers):
-        mods = []
-        for w, _ in layers:
-            mods += [nn.Linear(w.shape[1], w.shape[0]), act()]
-        return nn.Sequential(*mods)
-
-    class Extractor(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.shared_net, self.policy_net, self.value_net = seq(params.shared), seq(params.pi), seq(params.vf)
-
-    class Policy(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.log_std = nn.Parameter(torch.zeros(params.act_dim))
-            self.mlp_extractor = Extractor()
-            self.action_net = nn.Linear(params.action[0].shape[1], params.act_dim)
-            self.value_net = nn.Linear(params.value[0].shape[1], 1)
-
-        def evaluate_actions(self, obs, actions):
-            trunk = self.mlp_extractor.shared_net(obs)
-            mean = self.action_net(self.mlp_extractor.policy_net(trunk))
-            values = self.value_net(self.mlp_extractor.value_net(trunk))
-            dist = torch.distributions.Normal(mean, torch.ones_like(mean) * self.log_std.exp())
-            return values.flatten(), dist.log_prob(actions).sum(dim=1), dist.entropy().sum(dim=1)
-    model = Policy().double()
-    sd = {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in R.state_dict_from_params(params).items()}
-    model.load_state_dict(sd)
-    return model
-
-
-WRONG = ("no-clamp", "value-factor", "entropy-sign", "log-std-term")
-
-
-def sb3_loss(model, batch, clip, ent_coef, vf_coef, wrong=None):
-    """SB3's PPO.train() loss, literally.  ``wrong`` (one of WRONG) plants one mistake of the kind the
-    bound has to reject: the clamp left out, the value loss's factor 2 lost, the entropy term's sign
-    flipped, the -log_std term of the log-prob dropped from the gradient."""
-    import torch
-    import torch.nn.functional as F
-    obs, actions, old, adv, ret = (torch.from_numpy(np.asarray(a, np.float64)) for a in batch)
-    values, log_prob, entropy = model.evaluate_actions(obs, actions)
-    if wrong == "log-std-term":
-        log_prob = log_prob + model.log_std.sum() - model.log_std.sum().detach()
-    if wrong == "entropy-sign":
-        ent_coef = -ent_coef
-    if wrong == "value-factor":
-        vf_coef = vf_coef / 2
-    ratio = torch.exp(log_prob - old)
-    policy_loss_1 = adv * ratio
-    policy_loss_2 = adv * (ratio if wrong == "no-clamp" else torch.clamp(ratio, 1 - clip, 1 + clip))
-    policy_loss = -torch.min(policy_loss_1, policy_loss_2).mean()
-    clip_fraction = torch.mean((torch.abs(ratio - 1) > clip).double())
-    value_loss = F.mse_loss(ret, values)
-    entropy_loss = -torch.mean(entropy)
-    loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
-    log_ratio = log_prob - old
-    approx_kl = torch.mean((torch.exp(log_ratio) - 1) - log_ratio)
-    stats = [policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction]
-    return loss, np.array([float(s.detach()) for s in stats]), ratio.detach().numpy()
-
-
-def majorant(params, batch, clip, ent_coef, vf_coef):
-    """The a-priori error scale of every gradient entry: the rule's own backward pass in float64 with
-    every signed sum replaced by the sum of absolute values (|W|, |x|, |delta|, |act'| <= 1), so a
-    float32 rounding of relative size U anywhere moves an entry by at most U times this.  Returns the
-    flat majorant, the sensitivity factor and the operation count of the longest chain."""
-    obs, actions, old, adv, ret = (np.asarray(a, np.float64) for a in batch)
-    B = obs.shape[0]
-    f = (lambda x: np.tanh(x)) if params.activation == "tanh" else (lambda x: np.maximum(x, 0))
-    ab = lambda wb: (np.abs(wb[0].astype(np.float64)), np.abs(wb[1].astype(np.float64)))  # noqa: E731
-
-    def fwd(layers, x):
-        """The float64 activations of a tower and their absolute values (the layers' inputs' majorants)."""
-        xs = []
-        for w, b in layers:
-            x = f(x @ w.astype(np.float64).T + b)
-            xs.append(np.abs(x))
-        return x, xs
-    trunk, xs_sh = fwd(params.shared, obs)
-    fp, xs_pi = fwd(params.pi, trunk)
-    fv, xs_vf = fwd(params.vf, trunk)
-    wa, ba = ab(params.action)
-    wv, bv = ab(params.value)
-    mean = fp @ params.action[0].astype(np.float64).T + params.action[1]
-    v = (fv @ params.value[0].astype(np.float64).T + params.value[1])[:, 0]
-    mean_a, v_a = np.abs(fp) @ wa.T + ba, (np.abs(fv) @ wv.T + bv)[:, 0]
-    std = np.exp(params.log_std.astype(np.float64))
-    widths = [w.shape[1] for w, _ in params.shared + params.pi + params.vf + [params.action, params.value]]
-    depth = len(params.shared) + max(len(params.pi), len(params.vf)) + 1
-    # the longest chains: forward (the fan-ins of the layers in a row, the log-prob sum and exp) and
-    # backward (the fan-outs back down, a chunk of samples, the chunks)
-    n_fwd = sum(widths) + 2 * depth + 4 * params.act_dim + 8
-    n_bwd = sum(widths) + 2 * depth + min(B, R.CHUNK) + -(-B // R.CHUNK) + 16
-    d = actions - mean
-    # |d| and |v - ret| with the forward pass's a-priori absolute error (test_policy.py's forward bound)
-    d_a = np.abs(d) + n_fwd * U * (np.abs(actions) + mean_a)
-    dvr_a = np.abs(v - ret) + n_fwd * U * (v_a + np.abs(ret))
-    terms_a = (d_a * d_a) / (2 * std * std) + np.abs(params.log_std) + 1.0
-    lp = (-(d * d) / (2 * std * std) - params.log_std - 0.9189385332046727).sum(1)
-    ratio = np.exp(lp - old)
-    g_a = np.abs(adv) * ratio / B
-    dmean_a = g_a[:, None] * d_a / (std * std)
-    ls_a = g_a[:, None] * (d_a * d_a / (std * std) + 1) + abs(ent_coef)
-    dv_a = (2 * vf_coef * dvr_a / B)[:, None]
-    grads = {}
-
-    def bwd(layers, s_a, inputs_a, key):
-        for i in range(len(layers) - 1, -1, -1):
-            grads[key, i] = (s_a.T @ inputs_a[i], s_a.sum(0))        # |act'| <= 1
-            s_a = s_a @ np.abs(layers[i][0].astype(np.float64))
-        return s_a
-    grads["action", 0] = (dmean_a.T @ np.abs(fp), dmean_a.sum(0))
-    grads["value", 0] = (dv_a.T @ np.abs(fv), dv_a.sum(0))
-    s_pi = bwd(params.pi, dmean_a @ wa, [np.abs(trunk)] + xs_pi[:-1], "pi")
-    s_vf = bwd(params.vf, dv_a @ wv, [np.abs(trunk)] + xs_vf[:-1], "vf")
-    bwd(params.shared, s_pi + s_vf, [np.abs(obs)] + xs_sh[:-1], "shared")
-    parts = [ls_a.sum(0)]
-    for key, n in (("shared", len(params.shared)), ("pi", len(params.pi)), ("vf", len(params.vf)), ("action", 1), ("value", 1)):
-        for i in range(n):
-            parts += [grads[key, i][0].ravel(), grads[key, i][1]]
-    # sensitivity: a relative perturbation of the log-prob terms moves the ratio (and every policy
-    # gradient) by the size of the terms; one of an activation moves tanh' = 1 - t^2 by at most 2
-    # and a forward error of the mean moves d = action - mean, whose relative change |mean_a / d| enters
-    # dmean and the log_std term; that part is carried in d_a above
-    amp = 3.0 + terms_a.sum(1).max() + np.abs(lp - old).max()
-    return np.concatenate(parts), amp, n_bwd + amp * n_fwd
-
-
 _GRAD_CASES = {}
 
 
@@ -254,7 +52,7 @@ def grad_case(name, B):
 
 
 @pytest.mark.parametrize("B", BATCHES)
-@pytest.mark.parametrize("name", list(ARCHS))
+@pytest.mark.parametrize("name", NAMES)
 def test_rule_is_ppo(name, B):
     """ppo_grad_ref against autograd on SB3's loss in float64.  The bound is a priori: every float32
     operation of the rule carries a relative rounding of at most U; the longest dependency chain has
@@ -312,7 +110,7 @@ def test_rule_is_ppo(name, B):
 def test_evaluate_is_the_forward_rule():
     """The rule's evaluate step gives policy_ref's values and log-probs bit for bit on the actions
     policy_ref sampled, so on unchanged parameters the ratio is exactly 1 and approx_kl exactly 0."""
-    for name in ARCHS:
+    for name in NAMES:
         params = make_params(ARCHS[name], seed=2)
         rng = np.random.default_rng(4)
         obs = rng.standard_normal((37, params.obs_dim)).astype(np.float32)

@@ -5,10 +5,8 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-from test_ppo import make_batch, make_params
-from test_ppo_gpu import ARCHS, _dev, _same
-from test_ppo_options import KL_CASES, PERM_SEED, TRAIN_BATCH, TRAIN_EPOCHS, TRAIN_TOTAL, kl_run
-from test_ppo_options_gpu import HP, PER_EPOCH, _gen, _same_run, _snapshot, _train_buffer
+from ppo_cases import (ARCHS, HP, KL_CASES, PER_EPOCH, PERM_SEED, TRAIN_BATCH, TRAIN_EPOCHS, TRAIN_TOTAL, kl_run, make_batch, make_params, on_device,
+                       perm_gen, same, same_run, snapshot, train_buffer)
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd import ppo as R
@@ -36,10 +34,10 @@ def _ref_step(cur, state, parts, n_params, max_norm):
 def _check_state(pol, ppo, cur, state, what):
     got = pol.get_params()
     m, v = ppo.state()
-    _same(R.flatten_params(got), R.flatten_params(cur), f"{what}: parameters")
-    _same(got.std, cur.std, f"{what}: std")
-    _same(m, state.m, f"{what}: m")
-    _same(v, state.v, f"{what}: v")
+    same(R.flatten_params(got), R.flatten_params(cur), f"{what}: parameters")
+    same(got.std, cur.std, f"{what}: std")
+    same(m, state.m, f"{what}: m")
+    same(v, state.v, f"{what}: v")
 
 
 # ---- apply against the rule --------------------------------------------------------------------------
@@ -52,7 +50,7 @@ def test_apply_is_combine_and_adam(gpu_lib, name, B):
     multiple of the workgroup size, so the grid's tail holds parameters and the five statistics."""
     import torch
     params = make_params(ARCHS[name], seed=3)
-    batches = [_dev(make_batch(params, B, seed=30 + i)) for i in range(4)]
+    batches = [on_device(make_batch(params, B, seed=30 + i)) for i in range(4)]
     n = R.flatten_params(params).size
     if name == "sb3-default":
         assert n == 12493 and n % 64 and n % 256
@@ -70,7 +68,7 @@ def test_apply_is_combine_and_adam(gpu_lib, name, B):
             cur, row, coef = _ref_step(cur, state, parts, n, max_norm)
             coefs.append(coef)
             what = f"{name} B={B} R={ranks} step {step + 1}"
-            _same(stats, row, f"{what}: statistics row")
+            same(stats, row, f"{what}: statistics row")
             _check_state(pol, ppo, cur, state, what)
             assert torch.isnan(parts[:, n + 5:]).all(), "the padding is not written"
         assert coefs[0] < 1 and coefs[1] == 1 and coefs[2] < 1, coefs
@@ -111,10 +109,10 @@ def test_apply_hand_made_parts(gpu_lib):
     state = R.AdamState(n)
     cur, want_row, coef = _ref_step(params, state, parts, n, 1e6)
     assert coef == 1.0
-    _same(stats, want_row, "hand-made parts: the statistics row, signed zeros and the rank order included")
-    _same(stats, row, "the row")
+    same(stats, want_row, "hand-made parts: the statistics row, signed zeros and the rank order included")
+    same(stats, row, "the row")
     _check_state(pol, ppo, cur, state, "hand-made parts")
-    _same(parts, h, "parts is not written")
+    same(parts, h, "parts is not written")
     # the other rank order of the same rows gives other bits
     swapped = torch.from_numpy(np.ascontiguousarray(h[[0, 2, 1]])).cuda()
     pol2 = P.DevicePolicy.from_params(params)
@@ -124,15 +122,15 @@ def test_apply_hand_made_parts(gpu_lib):
     assert pol2.get_params().log_std[0] != pol.get_params().log_std[0]
     # the predicate: approx_kl above 1.5 * target_kl = 0 stops the call before anything is written
     ppo2.target_kl = 0.0
-    before = _snapshot(pol2, ppo2)
+    before = snapshot(pol2, ppo2)
     kl_parts = torch.from_numpy(h).cuda()
     kl_parts[:, n + 3] = 0.25
     out = torch.full((5,), 7.0, dtype=torch.float32, device="cuda")
     ppo2.apply(kl_parts, stats_out=out)
     want_out = R.combine_ref(kl_parts.cpu().numpy()[:, :n], kl_parts.cpu().numpy()[:, n:n + 5])[1]
-    _same(out, want_out, "the stopping call's combined row is recorded")
+    same(out, want_out, "the stopping call's combined row is recorded")
     assert (ppo2.t, ppo2.n_applied, ppo2.stopped) == (1, 0, True)
-    _same_run(_snapshot(pol2, ppo2), before, "a stopped apply")
+    same_run(snapshot(pol2, ppo2), before, "a stopped apply")
     for x in (ppo, ppo2, pol, pol2):
         x.close()
 
@@ -148,7 +146,7 @@ def test_dist_train_at_world_one_equals_plain_train(gpu_lib, mode):
     """One rank through the two-phase path (local gradient into exchange.mine, the copy-only exchange,
     apply with R = 1) equals plain train() bitwise: with normalize_advantage, and under a target_kl that
     stops in the first epoch."""
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     n = R.flatten_params(d["params"]).size
     lr, target_kl = KL_CASES["first-epoch"]
     for kl, norm in ((None, True), (target_kl, False)):
@@ -158,19 +156,19 @@ def test_dist_train_at_world_one_equals_plain_train(gpu_lib, mode):
         for dist_path in (False, True):
             pol = P.DevicePolicy.from_params(d["params"])
             ppo = R.DevicePPO(pol, exchange=_exchange(n, buf.n_lanes) if dist_path else None, **kw)
-            stats = ppo.train(buf, generator=_gen())
-            runs.append((_snapshot(pol, ppo), stats.cpu().numpy(), (ppo.t, ppo.n_applied, ppo.stopped)))
+            stats = ppo.train(buf, generator=perm_gen())
+            runs.append((snapshot(pol, ppo), stats.cpu().numpy(), (ppo.t, ppo.n_applied, ppo.stopped)))
             ppo.close()
             pol.close()
         what = f'"{mode}" target_kl={kl}'
-        _same_run(runs[1][0], runs[0][0], f"{what}: the dist path against plain train")
-        _same(runs[1][1], runs[0][1], f"{what}: statistics")
+        same_run(runs[1][0], runs[0][0], f"{what}: the dist path against plain train")
+        same(runs[1][1], runs[0][1], f"{what}: statistics")
         assert runs[1][2] == runs[0][2], what
         if kl is not None:
             want, want_stats, state = kl_run("first-epoch")
             stop = want_stats.shape[0] - 1
             assert runs[1][2] == (stop, stop, True)
-            _same_run(runs[1][0], (R.flatten_params(want), want.std, state.m, state.v), f"{what}: against ppo_train_ref")
+            same_run(runs[1][0], (R.flatten_params(want), want.std, state.m, state.v), f"{what}: against ppo_train_ref")
         else:
             assert runs[1][2] == (TRAIN_EPOCHS * PER_EPOCH, TRAIN_EPOCHS * PER_EPOCH, False)
 
@@ -180,36 +178,36 @@ def test_dist_train_predicate_and_a_following_train(gpu_lib):
     it is written: the parameters and moments, the later statistics rows, and exchange.mine, which still
     holds minibatch 0's local gradient and statistics.  A following train() works."""
     import torch
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     buf.log_probs.add_(0.5)
     n = R.flatten_params(d["params"]).size
     ex = _exchange(n, buf.n_lanes)
     pol = P.DevicePolicy.from_params(d["params"])
     ppo = R.DevicePPO(pol, learning_rate=LR, n_epochs=TRAIN_EPOCHS, batch_size=TRAIN_BATCH, normalize_advantage=False, target_kl=0.0,
                       minibatch="device", exchange=ex, **HP)
-    stats = ppo.train(buf, generator=_gen()).cpu().numpy()
+    stats = ppo.train(buf, generator=perm_gen()).cpu().numpy()
     assert (ppo.t, ppo.n_applied, ppo.stopped) == (0, 0, True)
     obs, actions, lp, adv, ret = d["data"]
     idx = d["epochs"][0][:TRAIN_BATCH]
     g0, s0 = R.ppo_grad_ref(d["params"], obs[idx], actions[idx], (lp + np.float32(0.5))[idx], adv[idx], ret[idx], **HP)
     assert s0[3] > 0
-    _same(stats[0], s0, "the stopping minibatch's row")
+    same(stats[0], s0, "the stopping minibatch's row")
     assert not stats[1:].any(), "the rows after the stop stay zero"
     mine = ex.mine.cpu().numpy()
-    _same(mine[:n], g0, "exchange.mine holds minibatch 0's gradient")
-    _same(mine[n:n + 5], s0, "and its statistics")
+    same(mine[:n], g0, "exchange.mine holds minibatch 0's gradient")
+    same(mine[n:n + 5], s0, "and its statistics")
     assert not mine[n + 5:].any()
-    _same(ex.parts.cpu().numpy()[0], mine, "parts is the copy of mine")
+    same(ex.parts.cpu().numpy()[0], mine, "parts is the copy of mine")
     zeros = np.zeros(n, np.float32)
-    _same_run(_snapshot(pol, ppo), (R.flatten_params(d["params"]), d["params"].std, zeros, zeros), "a stopped train")
+    same_run(snapshot(pol, ppo), (R.flatten_params(d["params"]), d["params"].std, zeros, zeros), "a stopped train")
     # a following train on the same object, against plain train on fresh parameters
     ppo.target_kl, ppo.n_epochs = None, 1
-    stats2 = ppo.train(buf, generator=_gen(PERM_SEED + 1))
+    stats2 = ppo.train(buf, generator=perm_gen(PERM_SEED + 1))
     pol_b = P.DevicePolicy.from_params(d["params"])
     ppo_b = R.DevicePPO(pol_b, learning_rate=LR, n_epochs=1, batch_size=TRAIN_BATCH, normalize_advantage=False, minibatch="device", **HP)
-    stats_b = ppo_b.train(buf, generator=_gen(PERM_SEED + 1))
-    _same(stats2, stats_b.cpu().numpy(), "a following train: statistics")
-    _same_run(_snapshot(pol, ppo), _snapshot(pol_b, ppo_b), "a following train")
+    stats_b = ppo_b.train(buf, generator=perm_gen(PERM_SEED + 1))
+    same(stats2, stats_b.cpu().numpy(), "a following train: statistics")
+    same_run(snapshot(pol, ppo), snapshot(pol_b, ppo_b), "a following train")
     assert ppo.t == ppo_b.t == PER_EPOCH and not ppo.stopped
     assert TRAIN_TOTAL == buf.n_steps * buf.n_lanes and torch.isfinite(stats2).all()
     for x in (ppo, ppo_b, pol, pol_b):
@@ -227,8 +225,8 @@ def test_set_state_round_trip_and_argument_errors(gpu_lib):
     ppo = R.DevicePPO(pol, learning_rate=LR, batch_size=8, **HP)
     ppo.set_state(m, v, 11)
     gm, gv = ppo.state()
-    _same(gm, m, "m after set_state")
-    _same(gv, v, "v after set_state")
+    same(gm, m, "m after set_state")
+    same(gv, v, "v after set_state")
     assert ppo.t == 11
     # the loaded state is the one the next step uses
     h = _hand_parts(n, n + 5)
@@ -244,7 +242,7 @@ def test_set_state_round_trip_and_argument_errors(gpu_lib):
         ppo.set_state(m[:-1], v, 0)
     with pytest.raises(ValueError):
         ppo.set_state(m, np.zeros(n + 1, np.float32), 0)
-    before = _snapshot(pol, ppo)
+    before = snapshot(pol, ppo)
     good = _zeros(2, n + 5)
     bad_calls = [
         lambda: ppo.apply(_zeros(0, n + 5)),                         # R = 0
@@ -272,7 +270,7 @@ def test_set_state_round_trip_and_argument_errors(gpu_lib):
     assert ppo.t == 13
     with pytest.raises(ValueError):
         R.DevicePPO(pol, exchange=GradExchange(Shard(0, 1, 4), n, torch.device("cuda", 0)))   # too few floats
-    _same(ppo.state()[0], (np.float32(0.9) * before[2] + np.float32(0.0)).astype(np.float32), "a zero gradient decays m; the refused calls changed nothing")
+    same(ppo.state()[0], (np.float32(0.9) * before[2] + np.float32(0.0)).astype(np.float32), "a zero gradient decays m; the refused calls changed nothing")
     pol.close()
     with pytest.raises(ValueError, match="closed"):
         ppo.apply(good)

@@ -4,20 +4,17 @@ SB3's loss on the union minibatch, the lockstep loop's bookkeeping, and the exch
 from __future__ import annotations
 
 import os
-import queue
-import socket
 import sys
 
 import numpy as np
 import pytest
-from test_ppo import ARCHS, U, majorant, make_batch, make_params, sb3_loss, torch_policy
-from test_ppo_options import TRAIN_BATCH, TRAIN_TOTAL, bits, train_data
+from ppo_cases import ARCHS, HP, TRAIN_BATCH, TRAIN_TOTAL, U, bits, majorant, make_batch, make_params, sb3_loss, torch_policy, train_data
+from ranks import ROOT, spawn
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd import ppo as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HP = dict(clip_range=0.2, ent_coef=0.01, vf_coef=0.5)
+NAMES = ("sb3-default", "odd-k-wide-head", "heads-only")
 BIG = np.float32(2.0 ** 60)
 
 
@@ -80,7 +77,7 @@ def test_combine_ref_order_and_signed_zeros():
 # ---- is it data-parallel PPO? ------------------------------------------------------------------------
 @pytest.mark.parametrize("B", (1, 33))
 @pytest.mark.parametrize("ranks", (2, 4))
-@pytest.mark.parametrize("name", list(ARCHS))
+@pytest.mark.parametrize("name", NAMES)
 def test_combined_gradient_is_ppo_on_the_union(name, ranks, B):
     """combine_ref of the ranks' ppo_grad_ref (no advantage normalisation) against float64 autograd of SB3's
     loss on the union minibatch.  The bound is a priori: the union's gradient is the mean of the ranks'
@@ -203,14 +200,6 @@ def test_train_dist_ref_unequal_minibatch_counts_raise():
 N_FLOATS = 70          # part_stride 128: the pad behind a rank's block travels too and stays zero
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _block(rank):
     return (np.arange(N_FLOATS, dtype=np.float32) + 1) * np.float32(rank + 1)
 
@@ -242,28 +231,8 @@ def _worker(rank, world, port, force, q):
         dist.destroy_process_group()
 
 
-def _spawn(world, force, target=None):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=target or _worker, args=(r, world, port, force, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = []
-    while len(results) < world:                     # a rank that died ends the wait at once
-        try:
-            results.append(q.get(timeout=0.2))
-        except queue.Empty:
-            assert all(p.is_alive() or p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return results
-
-
 def test_grad_exchange_two_gloo_ranks():
-    results = _spawn(2, False)
+    results = spawn(_worker, 2, False)
     assert sorted(r for r, _, _ in results) == [0, 1]
     for _, stride, parts in results:
         assert stride == 128 and parts.shape == (2, 128)
@@ -284,7 +253,7 @@ def test_grad_exchange_world_one():
     assert GradExchange(Shard(0, 1, 4), 64, "cpu").part_stride == 64 and GradExchange(Shard(0, 1, 4), 65, "cpu").part_stride == 128
     with pytest.raises(ValueError):
         GradExchange(Shard(0, 1, 4), 0, "cpu")
-    (rank, stride, forced), = _spawn(1, True)                       # the collective itself at world size 1
+    (rank, stride, forced), = spawn(_worker, 1, True)                       # the collective itself at world size 1
     assert rank == 0 and stride == 128 and np.array_equal(forced[0, :N_FLOATS], _block(0) + 1)
 
 
@@ -320,7 +289,7 @@ def _helpers_worker(rank, world, port, _, q):
 
 
 def test_agree_and_broadcast_array_two_gloo_ranks():
-    results = _spawn(2, False, target=_helpers_worker)
+    results = spawn(_helpers_worker, 2, False)
     assert sorted(r for r, _, _ in results) == [0, 1]
     want = np.array(_bits_vector(), np.float64).view(np.uint64)
     for _, msg, got in results:

@@ -4,41 +4,15 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-from test_ppo import exp_inputs, make_batch, make_params
+from ppo_cases import ARCHS, HP, exp_inputs, make_batch, make_params, on_device, same
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd import ppo as R
 
 pytestmark = pytest.mark.gpu
 
-# tests/test_policy_gpu.py's ARCHS, and a layer of width 1 behind another layer: its backward product has a
-# single k term (no matrix step at all) and its row-major weight image a single row
-ARCHS = {
-    "sb3-default": (28, 6, (0, 2, 2), [64, 64, 64, 64], "tanh"),
-    "reference-config": (28, 6, (2, 0, 0), [256, 256], "tanh"),
-    "odd-k-wide-head": (27, 15, (1, 1, 1), [40, 24, 8], "relu"),
-    "heads-only": (69, 4, (0, 0, 0), [], "tanh"),
-    "one-by-one": (1, 1, (0, 1, 0), [1], "relu"),
-    "width-one-inside": (32, 2, (2, 0, 0), [31, 1], "tanh"),
-    "width-one-towers": (7, 2, (1, 1, 1), [8, 1, 1], "relu"),
-}
+NAMES = ("sb3-default", "reference-config", "odd-k-wide-head", "heads-only", "one-by-one", "width-one-inside", "width-one-towers")
 BATCHES = (1, 31, 33, 256, 257, 600)   # partial tiles, a second workgroup, the chunk edge, a short chunk after two full ones
-HP = dict(clip_range=0.2, ent_coef=0.01, vf_coef=0.5)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    bad = np.flatnonzero(_bits(got).ravel() != _bits(want).ravel())
-    assert bad.size == 0, f"{what}: {bad.size} of {want.size} differ, first at {bad[:5]}: {got.ravel()[bad[:5]]} != {want.ravel()[bad[:5]]}"
-
-
-def _dev(batch):
-    import torch
-    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in batch]
 
 
 def _ppo(params, max_batch, **kw):
@@ -52,7 +26,7 @@ def test_exp_on_the_device(gpu_lib):
     assert x.size >= 500_000 and np.isnan(x).any() and np.isinf(x).any()
     out = np.zeros_like(x)
     assert gpu_lib.mrp_selftest_exp(0, _native._p(x), _native._p(out), x.size) == 0
-    _same(out, R.exp_ref(x), "exp_f32 on the device against exp_ref")
+    same(out, R.exp_ref(x), "exp_f32 on the device against exp_ref")
 
 
 _CASES = {}
@@ -66,7 +40,7 @@ def _case(name):
     return _CASES[name]
 
 
-@pytest.mark.parametrize("name", list(ARCHS))
+@pytest.mark.parametrize("name", NAMES)
 def test_bitwise_grad(gpu_lib, name):
     params, batch = _case(name)
     sizes = [B for B in BATCHES if B <= batch[0].shape[0]]
@@ -75,10 +49,10 @@ def test_bitwise_grad(gpu_lib, name):
     for B in sizes:
         sub = tuple(a[:B] for a in batch)
         want_g, want_s = R.ppo_grad_ref(params, *sub, **HP)
-        g, s = ppo.grad(*_dev(sub))
-        _same(s, want_s, f"{name} B={B} statistics")
-        _same(g, want_g, f"{name} B={B} flat gradient")
-    _same(R.flatten_params(pol.get_params()), R.flatten_params(params), "grad leaves the parameters alone")
+        g, s = ppo.grad(*on_device(sub))
+        same(s, want_s, f"{name} B={B} statistics")
+        same(g, want_g, f"{name} B={B} flat gradient")
+    same(R.flatten_params(pol.get_params()), R.flatten_params(params), "grad leaves the parameters alone")
     ppo.close()
     pol.close()
 
@@ -124,9 +98,9 @@ def test_zeros_and_negative_zeros_backward(gpu_lib, name):
     assert (np.signbit(want_g) & (want_g == 0)).any(), "the case holds negative zeros"
     assert ((want_g == 0) & ~np.signbit(want_g)).any() and (want_g != 0).any()
     pol, ppo = _ppo(params, batch[0].shape[0])
-    g, s = ppo.grad(*_dev(batch))
-    _same(g, want_g, f"{name} flat gradient")
-    _same(s, want_s, f"{name} statistics")
+    g, s = ppo.grad(*on_device(batch))
+    same(g, want_g, f"{name} flat gradient")
+    same(s, want_s, f"{name} statistics")
     ppo.close()
     pol.close()
 
@@ -144,7 +118,7 @@ def test_three_steps(gpu_lib, name, max_norm):
     runs = []
     for _ in range(2):
         pol, ppo = _ppo(params, B, learning_rate=lr, max_grad_norm=max_norm)
-        stats = [ppo.step(*_dev(b)).clone() for b in batches]
+        stats = [ppo.step(*on_device(b)).clone() for b in batches]
         runs.append((pol, ppo, stats))
     state, cur = R.AdamState(R.flatten_params(params).size), params
     coefs = []
@@ -152,32 +126,32 @@ def test_three_steps(gpu_lib, name, max_norm):
         grad, _ = R.ppo_grad_ref(cur, *b, **HP)
         coefs.append(float(R.clip_coef_ref(grad, max_norm)))
         cur, want_s = R.ppo_step_ref(cur, state, b, lr=lr, max_grad_norm=max_norm, **HP)
-        _same(runs[0][2][i], want_s, f"step {i + 1} statistics")
+        same(runs[0][2][i], want_s, f"step {i + 1} statistics")
     assert all(c < 1 for c in coefs) if max_norm == 0.5 else all(c == 1 for c in coefs), coefs
     pol, ppo, _ = runs[0]
     assert ppo.t == 3 and state.t == 3
     got = pol.get_params()
-    _same(R.flatten_params(got), R.flatten_params(cur), "parameters after three steps")
-    _same(got.std, cur.std, "std")
-    _same(got.std, R.exp_ref(got.log_std), "std is exp_ref(log_std)")
+    same(R.flatten_params(got), R.flatten_params(cur), "parameters after three steps")
+    same(got.std, cur.std, "std")
+    same(got.std, R.exp_ref(got.log_std), "std is exp_ref(log_std)")
     m, v = ppo.state()
-    _same(m, state.m, "m")
-    _same(v, state.v, "v")
+    same(m, state.m, "m")
+    same(v, state.v, "v")
     sd = pol.state_dict()
-    _same(R.flatten_params(P.params_from_state_dict(sd, params.activation)), R.flatten_params(cur), "state_dict")
+    same(R.flatten_params(P.params_from_state_dict(sd, params.activation)), R.flatten_params(cur), "state_dict")
     # act after step uses the new parameters
     rng = np.random.default_rng(5)
     obs = rng.standard_normal((70, params.obs_dim)).astype(np.float32)
     eps = rng.standard_normal((70, params.act_dim)).astype(np.float32)
     out = pol.act(torch.from_numpy(obs).cuda(), eps=torch.from_numpy(eps).cuda())
     for g, w, what in zip(out, P.policy_ref(got, obs, eps), ("actions", "clipped", "values", "log_probs")):
-        _same(g, w, f"act after step: {what}")
+        same(g, w, f"act after step: {what}")
     # the second run
     pol2, ppo2, stats2 = runs[1]
-    _same(R.flatten_params(pol2.get_params()), R.flatten_params(got), "a second run: parameters")
-    _same(torch.stack(stats2), torch.stack(runs[0][2]).cpu().numpy(), "a second run: statistics")
+    same(R.flatten_params(pol2.get_params()), R.flatten_params(got), "a second run: parameters")
+    same(torch.stack(stats2), torch.stack(runs[0][2]).cpu().numpy(), "a second run: statistics")
     for a, b in zip(ppo2.state(), (m, v)):
-        _same(a, b, "a second run: moments")
+        same(a, b, "a second run: moments")
     for p_, o_, _ in runs:
         o_.close()
         p_.close()
@@ -216,9 +190,9 @@ def test_train_end_to_end(gpu_lib):
     state = R.AdamState(ppo.n_params)
     want, want_stats = R.ppo_train_ref(params, state, data, epochs, 256, lr=3e-4, **hp)
     got = pol.get_params()
-    _same(stats, want_stats, "train statistics")
-    _same(R.flatten_params(got), R.flatten_params(want), "parameters after train")
-    _same(got.std, want.std, "std after train")
+    same(stats, want_stats, "train statistics")
+    same(R.flatten_params(got), R.flatten_params(want), "parameters after train")
+    same(got.std, want.std, "std after train")
     # normalize_advantage: train equals step on the torch-normalised advantages
     pa = P.DevicePolicy.from_params(params)
     pb = P.DevicePolicy.from_params(params)
@@ -227,7 +201,7 @@ def test_train_end_to_end(gpu_lib):
     ta.train(buf, generator=torch.Generator(device="cpu").manual_seed(9))
     for o, a, _, lp, adv, ret in buf.get(256, torch.Generator(device="cpu").manual_seed(9)):
         tb.step(o, a, lp, (adv - adv.mean()) / (adv.std() + 1e-8), ret)
-    _same(R.flatten_params(pa.get_params()), R.flatten_params(pb.get_params()), "normalize_advantage")
+    same(R.flatten_params(pa.get_params()), R.flatten_params(pb.get_params()), "normalize_advantage")
     assert not np.array_equal(R.flatten_params(pa.get_params()), R.flatten_params(params))
     # a second rollout with the trained policy
     collect_rollouts(env, pol, buf, *nxt)
@@ -243,11 +217,11 @@ def test_inputs_are_not_written_and_argument_errors(gpu_lib):
     B = 40
     sub = tuple(a[:B] for a in batch)
     pol, ppo = _ppo(params, B)
-    d = _dev(sub)
+    d = on_device(sub)
     ppo.grad(*d)
     ppo.step(*d)
     for t, a, what in zip(d, sub, ("obs", "actions", "old_log_probs", "advantages", "returns")):
-        _same(t, a, f"{what} after the launches")
+        same(t, a, f"{what} after the launches")
     z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device="cuda")  # noqa: E731
     obs, act, old, adv, ret = d
     bad_calls = [
@@ -288,7 +262,7 @@ def test_inputs_are_not_written_and_argument_errors(gpu_lib):
     empty.set_params(params)
     g, _ = e_ppo.grad(*d)
     g0, _ = ppo_fresh_grad(params, d, B)
-    _same(g, g0, "gradient after a late set_params")
+    same(g, g0, "gradient after a late set_params")
     for x in (e_ppo, ppo, empty, pol):
         x.close()
 
@@ -298,7 +272,7 @@ def test_calls_after_the_policy_is_closed_are_refused(gpu_lib):
     memory, so DevicePPO checks the policy's handle first."""
     params, batch = _case("sb3-default")
     B = 40
-    d = _dev(tuple(a[:B] for a in batch))
+    d = on_device(tuple(a[:B] for a in batch))
     pol, ppo = _ppo(params, B)
     ppo.step(*d)
     pol.close()

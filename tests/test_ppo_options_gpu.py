@@ -7,18 +7,13 @@ import copy
 
 import numpy as np
 import pytest
-from test_ppo import make_batch, make_params
-from test_ppo_gpu import ARCHS, _dev, _same
-from test_ppo_options import (CV, KL_CASES, PERM_SEED, TRAIN_BATCH, TRAIN_EPOCHS, TRAIN_N, TRAIN_T, TRAIN_TOTAL, _normalize_by_hand,
-                              kl_run, make_old_values, train_data, train_epochs)
+from ppo_cases import (ARCHS, CV, HP, KL_CASES, PER_EPOCH, TRAIN_BATCH, TRAIN_EPOCHS, fill_buffer, kl_run, make_batch, make_old_values, make_params,
+                       normalize_by_hand, on_device, perm_gen, same, same_run, snapshot, train_buffer, train_epochs)
 
 from gym_puzzles_amd import policy as P
 from gym_puzzles_amd import ppo as R
 
 pytestmark = pytest.mark.gpu
-
-HP = dict(clip_range=0.2, ent_coef=0.01, vf_coef=0.5)
-PER_EPOCH = -(-TRAIN_TOTAL // TRAIN_BATCH)
 
 
 def _t(a):
@@ -47,25 +42,18 @@ def test_bitwise_grad_clip_range_vf(gpu_lib, name, B):
     assert not np.array_equal(want_g, plain_g) or B == 1
     pol = P.DevicePolicy.from_params(params)
     ppo = R.DevicePPO(pol, batch_size=B, clip_range_vf=CV, **HP)
-    g, s = ppo.grad(*_dev(batch), old_values=_t(old_v))
-    _same(s, want_s, f"{name} B={B} statistics")
-    _same(g, want_g, f"{name} B={B} flat gradient")
+    g, s = ppo.grad(*on_device(batch), old_values=_t(old_v))
+    same(s, want_s, f"{name} B={B} statistics")
+    same(g, want_g, f"{name} B={B} flat gradient")
     assert ppo.progress() == (False, 0)
-    _same(R.flatten_params(pol.get_params()), R.flatten_params(params), "grad leaves the parameters alone")
+    same(R.flatten_params(pol.get_params()), R.flatten_params(params), "grad leaves the parameters alone")
     with pytest.raises(ValueError, match="old_values"):
-        ppo.grad(*_dev(batch))
+        ppo.grad(*on_device(batch))
     ppo.close()
     pol.close()
 
 
 # ---- gather and normalisation ------------------------------------------------------------------------
-def _fill(buf, fields):
-    import torch
-    for t, a in zip((buf.observations, buf.actions, buf.values, buf.log_probs, buf.advantages, buf.returns), fields):
-        t.copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(t.shape))
-    buf.pos, buf.full = buf.n_steps, True
-
-
 _GATHER = {}
 
 
@@ -84,7 +72,7 @@ def _check_staged(staged, fields, idx, want_adv, what):
     obs, actions, values, old, adv, ret = fields
     for key, rows in (("obs", obs[idx]), ("actions", actions[idx]), ("old_values", values[idx]), ("old_log_probs", old[idx]),
                       ("returns", ret[idx]), ("advantages", want_adv)):
-        _same(staged[key], rows, f"{what}: staged {key}")
+        same(staged[key], rows, f"{what}: staged {key}")
 
 
 @pytest.mark.parametrize("B", (1, 2, 255, 256, 257, 640))
@@ -94,7 +82,7 @@ def test_gather_and_normalise(gpu_lib, B):
     from gym_puzzles_amd import DeviceRolloutBuffer
     params, fields = gather_case()
     buf = DeviceRolloutBuffer(16, 40, (params.obs_dim,), params.act_dim, device=0)
-    _fill(buf, fields)
+    fill_buffer(buf, fields)
     idx = np.random.default_rng(B).permutation(640)[:B].astype(np.int64)
     pol = P.DevicePolicy.from_params(params)
     ppo = R.DevicePPO(pol, batch_size=640, clip_range_vf=CV, **HP)
@@ -105,19 +93,19 @@ def test_gather_and_normalise(gpu_lib, B):
         _check_staged(ppo.staged(), fields, idx, want_adv, f"B={B} normalize={normalize}")
         want_g, want_s = R.ppo_grad_ref(params, fields[0][idx], fields[1][idx], fields[3][idx], want_adv, fields[5][idx], **HP,
                                         old_values=fields[2][idx], clip_range_vf=CV)
-        _same(s, want_s, f"B={B} normalize={normalize}: statistics")
-        _same(g, want_g, f"B={B} normalize={normalize}: flat gradient")
+        same(s, want_s, f"B={B} normalize={normalize}: statistics")
+        same(g, want_g, f"B={B} normalize={normalize}: flat gradient")
     assert ppo.progress() == (False, 0)
     if B == 640:
         # the chunk order of the two sums: +-2^60 as the last sample of chunk 0 and the first of chunk 1
         big = fields[4].copy()
         big[idx[255]], big[idx[256]] = 2.0 ** 60, -2.0 ** 60
         want = R.normalize_adv_ref(big[idx])
-        assert not np.array_equal(want, _normalize_by_hand(big[idx], 640)), "the input tells the chunk order from a flat sum"
+        assert not np.array_equal(want, normalize_by_hand(big[idx], 640)), "the input tells the chunk order from a flat sum"
         ppo.grad(obs, actions, old, _t(big), ret, old_values=values, index=_t(idx), normalize=True)
-        _same(ppo.staged()["advantages"], want, "normalised advantages, chunk order")
+        same(ppo.staged()["advantages"], want, "normalised advantages, chunk order")
     for t, a in zip((obs, actions, values, old, adv, ret), fields):
-        _same(t, a, "the fields are not written")
+        same(t, a, "the fields are not written")
     ppo.close()
     pol.close()
 
@@ -154,55 +142,30 @@ def test_gather_bad_indices(gpu_lib):
 
 
 # ---- train -------------------------------------------------------------------------------------------
-def _train_buffer():
-    from gym_puzzles_amd import DeviceRolloutBuffer
-    d = train_data()
-    obs, actions, lp, adv, ret = d["data"]
-    buf = DeviceRolloutBuffer(TRAIN_T, TRAIN_N, (d["params"].obs_dim,), d["params"].act_dim, device=0)
-    _fill(buf, (obs, actions, d["values"], lp, adv, ret))
-    return d, buf
-
-
-def _gen(seed=PERM_SEED):
-    import torch
-    return torch.Generator(device="cpu").manual_seed(seed)
-
-
-def _snapshot(pol, ppo):
-    got = pol.get_params()
-    m, v = ppo.state()
-    return R.flatten_params(got), got.std, m, v
-
-
-def _same_run(a, b, what):
-    for x, y, part in zip(a, b, ("parameters", "std", "m", "v")):
-        _same(x, y, f"{what}: {part}")
-
-
 def test_train_device_gather_end_to_end(gpu_lib):
     """600 samples, batch 128, 2 epochs: "device" equals "torch" bitwise without normalisation; with it,
     "device" equals ppo_train_ref(normalize_advantage=True); a second object gives identical bits."""
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     kw = dict(learning_rate=1e-3, n_epochs=TRAIN_EPOCHS, batch_size=TRAIN_BATCH, **HP)
     runs = {}
     for key, mode, norm in (("torch", "torch", False), ("device", "device", False), ("norm", "device", True), ("norm2", "device", True)):
         pol = P.DevicePolicy.from_params(d["params"])
         ppo = R.DevicePPO(pol, normalize_advantage=norm, minibatch=mode, **kw)
-        stats = ppo.train(buf, generator=_gen())
+        stats = ppo.train(buf, generator=perm_gen())
         assert tuple(stats.shape) == (TRAIN_EPOCHS * PER_EPOCH, 5) and ppo.t == TRAIN_EPOCHS * PER_EPOCH
         assert ppo.n_applied == TRAIN_EPOCHS * PER_EPOCH and not ppo.stopped
-        runs[key] = (_snapshot(pol, ppo), stats.cpu().numpy())
+        runs[key] = (snapshot(pol, ppo), stats.cpu().numpy())
         ppo.close()
         pol.close()
-    _same_run(runs["device"][0], runs["torch"][0], '"device" against "torch"')
-    _same(runs["device"][1], runs["torch"][1], '"device" against "torch": statistics')
+    same_run(runs["device"][0], runs["torch"][0], '"device" against "torch"')
+    same(runs["device"][1], runs["torch"][1], '"device" against "torch": statistics')
     state = R.AdamState(R.flatten_params(d["params"]).size)
     want, want_stats = R.ppo_train_ref(d["params"], state, d["data"], d["epochs"], TRAIN_BATCH, lr=1e-3, normalize_advantage=True, **HP)
-    _same_run(runs["norm"][0], (R.flatten_params(want), want.std, state.m, state.v), "normalize_advantage against ppo_train_ref")
-    _same(runs["norm"][1], want_stats, "normalize_advantage: statistics")
+    same_run(runs["norm"][0], (R.flatten_params(want), want.std, state.m, state.v), "normalize_advantage against ppo_train_ref")
+    same(runs["norm"][1], want_stats, "normalize_advantage: statistics")
     assert not np.array_equal(runs["norm"][0][0], runs["device"][0][0])
-    _same_run(runs["norm2"][0], runs["norm"][0], "a second object")
-    _same(runs["norm2"][1], runs["norm"][1], "a second object: statistics")
+    same_run(runs["norm2"][0], runs["norm"][0], "a second object")
+    same(runs["norm2"][1], runs["norm"][1], "a second object: statistics")
 
 
 @pytest.mark.parametrize("mode", ["device", "torch"])
@@ -210,7 +173,7 @@ def test_train_device_gather_end_to_end(gpu_lib):
 def test_train_target_kl(gpu_lib, case, mode):
     """The stop decided on the device: everything equals ppo_train_ref's, the minibatches after the stop
     leave nothing behind, and polling once per epoch changes no bit."""
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     lr, target_kl = KL_CASES[case]
     want, want_stats, state = kl_run(case)
     stop = want_stats.shape[0] - 1
@@ -222,9 +185,9 @@ def test_train_target_kl(gpu_lib, case, mode):
     for poll in (False, True):
         pol = P.DevicePolicy.from_params(d["params"])
         ppo = R.DevicePPO(pol, **kw)
-        stats = ppo.train(buf, generator=_gen(), poll=poll)
-        _same(stats, full, f"{case} poll={poll}: the statistics rows, zeros after the stop")
-        _same_run(_snapshot(pol, ppo), ref, f"{case} poll={poll}")
+        stats = ppo.train(buf, generator=perm_gen(), poll=poll)
+        same(stats, full, f"{case} poll={poll}: the statistics rows, zeros after the stop")
+        same_run(snapshot(pol, ppo), ref, f"{case} poll={poll}")
         assert (ppo.t, ppo.n_applied, ppo.stopped) == (stop, stop, True) and state.t == stop
         ppo.close()
         pol.close()
@@ -233,7 +196,7 @@ def test_train_target_kl(gpu_lib, case, mode):
 def test_train_after_a_stop_continues_the_rule(gpu_lib):
     """A second train() on the same object: the words are cleared, t is carried into Adam's bias
     correction, and the generator goes on where the first call left it."""
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     case = "first-epoch"
     lr, target_kl = KL_CASES[case]
     first, first_stats, state = kl_run(case)
@@ -243,14 +206,14 @@ def test_train_after_a_stop_continues_the_rule(gpu_lib):
     pol = P.DevicePolicy.from_params(d["params"])
     ppo = R.DevicePPO(pol, learning_rate=lr, n_epochs=TRAIN_EPOCHS, batch_size=TRAIN_BATCH, normalize_advantage=False,
                       target_kl=target_kl, minibatch="device", **HP)
-    gen = _gen()
+    gen = perm_gen()
     ppo.train(buf, generator=gen)
     ppo.n_epochs, ppo.target_kl = 1, 10 * target_kl
     stats = ppo.train(buf, generator=gen)              # resolves t from the device first
     n = want_stats.shape[0]
-    _same(stats[:n], want_stats, "the second call's statistics")
+    same(stats[:n], want_stats, "the second call's statistics")
     assert not stats[n:].any()
-    _same_run(_snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), "the rule continued")
+    same_run(snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), "the rule continued")
     assert ppo.t == state.t == stop + ppo.n_applied
     assert ppo.stopped == R.kl_stop_ref(want_stats[-1, 3], 10 * target_kl), "the reference's last row is its stopping row, if any"
     ppo.close()
@@ -258,18 +221,18 @@ def test_train_after_a_stop_continues_the_rule(gpu_lib):
 
 
 def test_target_kl_never_reached_and_with_clip_range_vf(gpu_lib):
-    d, buf = _train_buffer()
+    d, buf = train_buffer()
     runs = []
     for target_kl in (1e9, None):
         pol = P.DevicePolicy.from_params(d["params"])
         ppo = R.DevicePPO(pol, n_epochs=1, batch_size=TRAIN_BATCH, normalize_advantage=True, target_kl=target_kl, minibatch="device", **HP)
-        stats = ppo.train(buf, generator=_gen())
+        stats = ppo.train(buf, generator=perm_gen())
         assert (ppo.t, ppo.n_applied, ppo.stopped) == (PER_EPOCH, PER_EPOCH, False)
-        runs.append((_snapshot(pol, ppo), stats.cpu().numpy()))
+        runs.append((snapshot(pol, ppo), stats.cpu().numpy()))
         ppo.close()
         pol.close()
-    _same_run(runs[0][0], runs[1][0], "a target never reached against no target")
-    _same(runs[0][1], runs[1][1], "a target never reached: statistics")
+    same_run(runs[0][0], runs[1][0], "a target never reached against no target")
+    same(runs[0][1], runs[1][1], "a target never reached: statistics")
     # clip_range_vf together with target_kl
     case = "first-epoch"
     lr, target_kl = KL_CASES[case]
@@ -279,10 +242,10 @@ def test_target_kl_never_reached_and_with_clip_range_vf(gpu_lib):
     pol = P.DevicePolicy.from_params(d["params"])
     ppo = R.DevicePPO(pol, learning_rate=lr, n_epochs=TRAIN_EPOCHS, batch_size=TRAIN_BATCH, normalize_advantage=False,
                       target_kl=target_kl, clip_range_vf=CV, minibatch="device", **HP)
-    stats = ppo.train(buf, generator=_gen())
-    _same(stats[:stop + 1], want_stats, "clip_range_vf with target_kl: statistics")
+    stats = ppo.train(buf, generator=perm_gen())
+    same(stats[:stop + 1], want_stats, "clip_range_vf with target_kl: statistics")
     assert not stats[stop + 1:].any()
-    _same_run(_snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), "clip_range_vf with target_kl")
+    same_run(snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), "clip_range_vf with target_kl")
     assert (ppo.t, ppo.stopped) == (stop, True)
     ppo.close()
     pol.close()
@@ -301,21 +264,21 @@ def test_train_without_options_after_a_stop(gpu_lib, mode):
     params = make_params(ARCHS["heads-only"], seed=1)
     obs, actions, old, adv, ret = make_batch(params, T * N, seed=9)     # moved log-probs: every approx_kl term is > 0
     buf = DeviceRolloutBuffer(T, N, (params.obs_dim,), params.act_dim, device=0)
-    _fill(buf, (obs, actions, P.values_ref(params, obs), old, adv, ret))
+    fill_buffer(buf, (obs, actions, P.values_ref(params, obs), old, adv, ret))
     pol = P.DevicePolicy.from_params(params)
     ppo = R.DevicePPO(pol, learning_rate=lr, n_epochs=1, batch_size=bs, normalize_advantage=False, target_kl=0.0, minibatch=mode, **HP)
-    ppo.train(buf, generator=_gen(7))
+    ppo.train(buf, generator=perm_gen(7))
     assert (ppo.stopped, ppo.n_applied, ppo.t) == (True, 0, 0)
-    _same(R.flatten_params(pol.get_params()), R.flatten_params(params), "the stopped call applies nothing")
+    same(R.flatten_params(pol.get_params()), R.flatten_params(params), "the stopped call applies nothing")
     ppo.target_kl = None
-    stats = ppo.train(buf, generator=_gen(11))
+    stats = ppo.train(buf, generator=perm_gen(11))
     assert (ppo.n_applied, ppo.t, ppo.stopped) == (2, 2, False)
-    perm = torch.randperm(T * N, generator=_gen(11)).numpy()
+    perm = torch.randperm(T * N, generator=perm_gen(11)).numpy()
     state = R.AdamState(R.flatten_params(params).size)
     want, want_stats = R.ppo_train_ref(params, state, (obs, actions, old, adv, ret), [(perm % T) * N + perm // T], bs, lr=lr,
                                        normalize_advantage=False, **HP)
-    _same(stats, want_stats, f"{mode}: statistics")
-    _same_run(_snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), f"{mode}: after the stop")
+    same(stats, want_stats, f"{mode}: statistics")
+    same_run(snapshot(pol, ppo), (R.flatten_params(want), want.std, state.m, state.v), f"{mode}: after the stop")
     ppo.close()
     pol.close()
 
@@ -349,6 +312,6 @@ def test_option_argument_errors(gpu_lib):
     with pytest.raises(ValueError):
         R.DevicePPO(pol, target_kl=-1.0)
     assert ppo.t == 0
-    _same(R.flatten_params(pol.get_params()), R.flatten_params(params), "refused calls change nothing")
+    same(R.flatten_params(pol.get_params()), R.flatten_params(params), "refused calls change nothing")
     ppo.close()
     pol.close()

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from ppo_cases import same
 
 from gym_puzzles_amd.rollout import gae_ref
 
@@ -46,13 +47,6 @@ def _run(d, gamma, lam, boot, **out):
                       d["tv"] if boot else None, **out)
 
 
-def _same(got, want, what):
-    got = got.cpu().numpy()
-    assert got.dtype == np.float32 and got.shape == want.shape, what
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert np.array_equal(got, want) and len(bad) == 0, f"{what}: {len(bad)} elements differ, first at {bad[:1]}"
-
-
 @pytest.mark.parametrize("boot", [False, True], ids=["plain", "bootstrap"])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_gae_device_bitwise(gpu_lib, shape, boot):
@@ -65,8 +59,8 @@ def test_gae_device_bitwise(gpu_lib, shape, boot):
     for gamma, lam in COEFFS:
         want_a, want_r = _ref(x, gamma, lam, boot)
         adv, ret = _run(d, gamma, lam, boot)
-        _same(adv, want_a, f"advantages {shape} gamma={gamma} lambda={lam}")
-        _same(ret, want_r, f"returns {shape} gamma={gamma} lambda={lam}")
+        same(adv, want_a, f"advantages {shape} gamma={gamma} lambda={lam}", typed=True)
+        same(ret, want_r, f"returns {shape} gamma={gamma} lambda={lam}", typed=True)
     # caller-provided outputs: the same tensors come back, with the same bytes
     A, Rt = torch.full((T, N), -7.0, device="cuda"), torch.full((T, N), -7.0, device="cuda")
     a2, r2 = _run(d, gamma, lam, boot, advantages=A, returns=Rt)
@@ -120,8 +114,8 @@ def test_rollout_end_to_end(gpu_lib):
     h = lambda t: t.cpu().numpy()  # noqa: E731
     args = (h(buf.rewards), h(buf.values), h(buf.episode_starts).astype(np.float32), h(last_values), h(done), 0.99, 0.95)
     want_a, want_r = gae_ref(*args, h(buf.truncated), h(buf.terminal_values))
-    _same(adv, want_a, "advantages")
-    _same(ret, want_r, "returns")
+    same(adv, want_a, "advantages", typed=True)
+    same(ret, want_r, "returns", typed=True)
     assert int(h(buf.truncated).sum()) >= 64
     plain_a, _ = gae_ref(*args)
     assert not np.array_equal(plain_a, want_a), "the bootstrap is visible in the advantages"
@@ -206,13 +200,13 @@ def test_gae_device_alias_rule_uses_byte_extents(gpu_lib):
     values.copy_(d["v"])
     with pytest.raises(ValueError, match="alias"):
         _run(dict(d, v=values), 0.99, 0.95, True, returns=returns)
-    _same(values, x["v"], "a refused call wrote nothing")
+    same(values, x["v"], "a refused call wrote nothing", typed=True)
     raw = torch.zeros(T * N + 4 * T * N, dtype=torch.uint8, device="cuda")
     starts, adv = raw[:T * N].view(T, N), raw[T * N:].view(torch.float32).view(T, N)  # advantages from byte 24 on
     starts.copy_(d["es"])
     want_a, want_r = _ref(x, 0.99, 0.95, True)
     got_a, got_r = _run(dict(d, es=starts), 0.99, 0.95, True, advantages=adv)
     assert got_a is adv
-    _same(got_a, want_a, "advantages behind episode_starts")
-    _same(got_r, want_r, "returns")
+    same(got_a, want_a, "advantages behind episode_starts", typed=True)
+    same(got_r, want_r, "returns", typed=True)
     assert np.array_equal(starts.cpu().numpy(), x["es"]), "episode_starts was written"

@@ -331,6 +331,11 @@ def case_id(case) -> str:
     return f"L{case[0]}-D{case[1]}-{case[2]}"
 
 
+def clips(args):
+    """(clip_obs, clip_reward) of a set of constructor arguments, as ``judge`` takes them."""
+    return args.get("clip_obs", 10.0), args.get("clip_reward", 10.0)
+
+
 def _columns(rs, L, D):
     """[L, D] float32; column j is of kind j % 7."""
     x = np.zeros((L, D), np.float64)

@@ -20,10 +20,7 @@ Shapes: 128 x 4096 (the project's lane count) and 4096 x 6 (the reference's ppo-
 4096, 6 envs).  Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -31,8 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from trainbench import bits, device_ms, lib_sha256, med, write_json  # noqa: E402
 
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
 from gym_puzzles_amd.rollout import gae_device, gae_ref  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -77,22 +74,6 @@ def torch_loop(r, v, es, lv, dones, trunc, tv, adv):
     return adv, adv + v
 
 
-def device_ms(fn, inner):
-    for _ in range(args.warmup):
-        fn()
-    torch.cuda.synchronize(dev)
-    out = []
-    for _ in range(args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(inner):
-            fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        out.append(e0.elapsed_time(e1) / inner)
-    return out
-
-
 def host_ms(fn):
     out = []
     for k in range(args.warmup + args.repeats):
@@ -105,12 +86,10 @@ def host_ms(fn):
     return out
 
 
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
 res = {"device": torch.cuda.get_device_name(dev), "gamma": GAMMA, "gae_lambda": LAMBDA, "repeats": args.repeats,
-       "warmup": args.warmup, "kernel_launches_per_repeat": args.inner, "libmrp_sha256": sha, "shapes": []}
+       "warmup": args.warmup, "kernel_launches_per_repeat": args.inner, "libmrp_sha256": lib_sha256(), "shapes": []}
 ok = True
-med = statistics.median
+timed = lambda fn, inner: device_ms(fn, inner, args.warmup, args.repeats, dev)  # noqa: E731
 for T, N in SHAPES:
     host_in = inputs(T, N, seed=T + N)
     r, v, es, lv, dones, trunc, tv = (torch.from_numpy(a).to(dev) for a in host_in)
@@ -132,12 +111,11 @@ for T, N in SHAPES:
 
     kernel()
     la, lr = loop()
-    bits = lambda a: a.view(np.uint32)  # noqa: E731
     same_k = bool(np.array_equal(bits(adv.cpu().numpy()), bits(want[0])) and np.array_equal(bits(ret.cpu().numpy()), bits(want[1])))
     same_t = bool(np.array_equal(bits(la.cpu().numpy()), bits(want[0])) and np.array_equal(bits(lr.cpu().numpy()), bits(want[1])))
     assert same_t, f"{T} x {N}: the torch loop does not reproduce gae_ref; it is not the same computation"
     assert same_k, f"{T} x {N}: mrp_gae_device differs from gae_ref"
-    k_ms, t_ms, h_ms = device_ms(kernel, args.inner), device_ms(loop, 1), host_ms(host)
+    k_ms, t_ms, h_ms = timed(kernel, args.inner), timed(loop, 1), host_ms(host)
     nbytes = T * N * ((4 + 2) * 4 + 2)
     row = {"n_steps": T, "n_lanes": N,
            "ms": {"kernel": med(k_ms), "torch_loop": med(t_ms), "host_gae_ref_with_copies": med(h_ms)},
@@ -149,9 +127,5 @@ for T, N in SHAPES:
     ok = ok and row["kernel_ahead"]
     res["shapes"].append(row)
 res["ok"] = ok
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)
 sys.exit(0 if ok else 1)

@@ -21,10 +21,7 @@ variants give the unsharded statistics and outputs bit for bit.
 Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -33,9 +30,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+from trainbench import bits, lib_sha256, summary, write_json  # noqa: E402
 
 from gym_puzzles_amd import DeviceVecNormalize  # noqa: E402
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
 from gym_puzzles_amd.dist import Shard  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -56,11 +53,6 @@ torch.cuda.set_device(dev)
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
 os.environ.setdefault("MASTER_PORT", "29518")
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
-
-
-def bits(t):
-    a = np.ascontiguousarray(t.cpu().numpy())
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def make(case):
@@ -86,7 +78,7 @@ class Step:
     def state(self):
         torch.cuda.synchronize(dev)
         st = self.norm.get_stats()
-        return [bits(x) for x in self.outs] + [np.atleast_1d(np.asarray(st[k], np.float64)).view(np.uint64) for k in sorted(st)]
+        return [bits(x, None) for x in self.outs] + [np.atleast_1d(np.asarray(st[k], np.float64)).view(np.uint64) for k in sorted(st)]
 
 
 g = torch.Generator(device="cpu").manual_seed(11)
@@ -140,17 +132,13 @@ for _ in range(args.repeats):
         device[case].append(t)
         ahead[case].append(bool(ok))
 
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
-med = statistics.median
 res = {"device": torch.cuda.get_device_name(dev), "lanes": LANES, "obs_dim": OBS, "repeats": args.repeats, "warmup": args.warmup,
-       "steps_per_repeat": args.inner, "libmrp_sha256": sha,
+       "steps_per_repeat": args.inner, "libmrp_sha256": lib_sha256(),
        "timer": "HIP events around steps_per_repeat enqueued steps: device = behind a spinning kernel, so the host enqueues "
                 "ahead; loop = the plain enqueueing loop",
        "backend": "nccl (RCCL) at world size 1; the collective case forces all_gather_into_tensor on device tensors",
        "not_measured": "no multi-rank RCCL exchange over xGMI has run", "sharded_equals_unsharded_bitwise": same,
        "launches": {"unsharded": 2, "copy": "3 + one device copy", "collective": "3 + all_gather_into_tensor"}}
-summary = lambda xs: {"median": med(xs), "min_max": [min(xs), max(xs)]}  # noqa: E731
 for case in CASES:
     res[case] = {"device_us_per_step": summary(device[case]), "loop_us_per_step": summary(loop[case]),
                  "host_enqueue_us_per_step": summary(host_us[case]), "host_ran_ahead_in": f"{sum(ahead[case])}/{args.repeats}"}
@@ -162,8 +150,4 @@ for key in ("device_us_per_step", "loop_us_per_step"):
 for s in steps.values():
     s.norm.close()
 dist.destroy_process_group()
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)

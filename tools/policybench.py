@@ -23,10 +23,7 @@ of the same network and is only checked to agree to 1e-4.
 Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,9 +31,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch import nn  # noqa: E402
+from trainbench import ACT, ARCHS, OBS, bench_params, bits, device_ms, lib_sha256, med, write_json  # noqa: E402
 
 from gym_puzzles_amd import policy as P  # noqa: E402
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=25)
@@ -51,26 +48,8 @@ if args.repeats < 20:
 if not torch.cuda.is_available():
     sys.exit("policybench: no HIP device visible; nothing measured")
 
-OBS, ACT, N = 28, 6, args.lanes
-ARCHS = (("sb3_default_pi64x2_vf64x2", [], [64, 64], [64, 64]), ("reference_shared256x2", [256, 256], [], []))
+N = args.lanes
 dev = torch.device("cuda", 0)
-
-
-def make_params(shared, pi, vf, seed):
-    rng = np.random.default_rng(seed)
-
-    def tower(k, widths):
-        out = []
-        for n in widths:
-            out.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32)))
-            k = n
-        return out, k
-    s, kt = tower(OBS, shared)
-    p, kp = tower(kt, pi)
-    v, kv = tower(kt, vf)
-    (a,), _ = tower(kp, [ACT])
-    (c,), _ = tower(kv, [1])
-    return P.PolicyParams(s, p, v, a, c, np.linspace(-0.5, 0.0, ACT).astype(np.float32), args.activation)
 
 
 def torch_modules(params):
@@ -88,32 +67,13 @@ def torch_modules(params):
     return trunk, pi, vf, torch.from_numpy(params.std).to(dev)
 
 
-def device_ms(fn):
-    for _ in range(args.warmup):
-        fn()
-    torch.cuda.synchronize(dev)
-    out = []
-    for _ in range(args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.inner):
-            fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        out.append(e0.elapsed_time(e1) / args.inner)
-    return out
-
-
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
 res = {"device": torch.cuda.get_device_name(dev), "obs_dim": OBS, "act_dim": ACT, "n_lanes": N, "activation": args.activation,
        "repeats": args.repeats,
-       "warmup": args.warmup, "calls_per_repeat": args.inner, "libmrp_sha256": sha, "archs": []}
+       "warmup": args.warmup, "calls_per_repeat": args.inner, "libmrp_sha256": lib_sha256(), "archs": []}
 ok = True
-med = statistics.median
-bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)  # noqa: E731
+timed = lambda fn: device_ms(fn, args.inner, args.warmup, args.repeats, dev)  # noqa: E731
 for name, shared, pi, vf in ARCHS:
-    params = make_params(shared, pi, vf, seed=len(name))
+    params = bench_params(shared, pi, vf, seed=len(name), activation=args.activation)
     rng = np.random.default_rng(1)
     obs, eps = rng.standard_normal((N, OBS)).astype(np.float32), rng.standard_normal((N, ACT)).astype(np.float32)
     d_obs, d_eps = torch.from_numpy(obs).to(dev), torch.from_numpy(eps).to(dev)
@@ -146,7 +106,7 @@ for name, shared, pi, vf in ARCHS:
     tout = torch_act()
     close = all(bool(torch.allclose(g, t, rtol=1e-4, atol=1e-4)) for g, t in zip(out, tout))
     assert close, f"{name}: the torch composition is not the same network"
-    f_ms, v_ms, t_ms = device_ms(fused), device_ms(values), device_ms(torch_act)
+    f_ms, v_ms, t_ms = timed(fused), timed(values), timed(torch_act)
     spread = max(max(f_ms) - min(f_ms), max(t_ms) - min(t_ms))
     row = {"arch": name, "ms": {"act": med(f_ms), "values": med(v_ms), "torch_act": med(t_ms)},
            "ms_min_max": {"act": [min(f_ms), max(f_ms)], "values": [min(v_ms), max(v_ms)], "torch_act": [min(t_ms), max(t_ms)]},
@@ -156,9 +116,5 @@ for name, shared, pi, vf in ARCHS:
     res["archs"].append(row)
     pol.close()
 res["ok"] = ok
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)
 sys.exit(0 if ok else 1)

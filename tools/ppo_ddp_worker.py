@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+from trainbench import bench_params  # noqa: E402
 
 from gym_puzzles_amd import DeviceRolloutBuffer, MultiRobotPuzzleVecEnv  # noqa: E402
 from gym_puzzles_amd import policy as P  # noqa: E402
@@ -29,22 +30,6 @@ from gym_puzzles_amd.rollout import collect_rollouts  # noqa: E402
 
 LANES, T, EPOCHS, BATCH = 8, 16, 2, 32
 HP = dict(learning_rate=1e-3, clip_range=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5)
-
-
-def make_params(obs_dim, act_dim, seed):
-    rng = np.random.default_rng(seed)
-
-    def tower(k, widths):
-        out = []
-        for n in widths:
-            out.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32)))
-            k = n
-        return out, k
-    p, kp = tower(obs_dim, [64, 64])
-    v, kv = tower(obs_dim, [64, 64])
-    (a,), _ = tower(kp, [act_dim])
-    (c,), _ = tower(kv, [1])
-    return P.PolicyParams([], p, v, a, c, np.linspace(-0.5, 0.0, act_dim).astype(np.float32), "tanh")
 
 
 def main():
@@ -60,7 +45,7 @@ def main():
     try:
         env = MultiRobotPuzzleVecEnv("MultiRobotPuzzle-v0", LANES, seed=3, lane_offset=shard.lane_offset, max_episode_steps=5)
         O, A = env.observation_space.shape[0], env.action_space.shape[0]
-        pol = P.DevicePolicy.from_params(make_params(O, A, seed=10 + shard.rank), seed=77, lane_offset=shard.lane_offset)
+        pol = P.DevicePolicy.from_params(bench_params([], [64, 64], [64, 64], 10 + shard.rank, obs_dim=O, act_dim=A), seed=77, lane_offset=shard.lane_offset)
         n = pol.n_params
         ppo = R.DevicePPO(pol, n_epochs=EPOCHS, batch_size=BATCH, normalize_advantage=True, target_kl=1e9, minibatch="device",
                           exchange=GradExchange(shard, n + 5, dev, host_stage=True), **HP)

@@ -21,10 +21,7 @@ timed the tool asserts that one fused step on a 128-sample minibatch equals the 
 Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,10 +30,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from torch import nn  # noqa: E402
+from trainbench import ACT, ARCHS, OBS, bench_params, bits, device_ms, lib_sha256, med, write_json  # noqa: E402
 
 from gym_puzzles_amd import policy as P  # noqa: E402
 from gym_puzzles_amd import ppo as R  # noqa: E402
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=25)
@@ -49,29 +46,10 @@ if args.repeats < 20:
 if not torch.cuda.is_available():
     sys.exit("ppobench: no HIP device visible; nothing measured")
 
-OBS, ACT = 28, 6
 BATCHES = (128, 4096, 16384)
-ARCHS = (("sb3_default_pi64x2_vf64x2", [], [64, 64], [64, 64]), ("reference_shared256x2", [256, 256], [], []))
 HP = dict(clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5)
 LR = 3e-4
 dev = torch.device("cuda", 0)
-
-
-def make_params(shared, pi, vf, seed):
-    rng = np.random.default_rng(seed)
-
-    def tower(k, widths):
-        out = []
-        for n in widths:
-            out.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32)))
-            k = n
-        return out, k
-    s, kt = tower(OBS, shared)
-    p, kp = tower(kt, pi)
-    v, kv = tower(kt, vf)
-    (a,), _ = tower(kp, [ACT])
-    (c,), _ = tower(kv, [1])
-    return P.PolicyParams(s, p, v, a, c, np.linspace(-0.5, 0.0, ACT).astype(np.float32), "tanh")
 
 
 def make_batch(params, B, seed):
@@ -132,30 +110,11 @@ def torch_stepper(params, batch):
     return step
 
 
-def device_ms(fn):
-    for _ in range(args.warmup):
-        fn()
-    torch.cuda.synchronize(dev)
-    out = []
-    for _ in range(args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.inner):
-            fn()
-        e1.record()
-        torch.cuda.synchronize(dev)
-        out.append(e0.elapsed_time(e1) / args.inner)
-    return out
-
-
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
 res = {"device": torch.cuda.get_device_name(dev), "obs_dim": OBS, "act_dim": ACT, "repeats": args.repeats, "warmup": args.warmup,
-       "steps_per_repeat": args.inner, "libmrp_sha256": sha, "hyperparameters": dict(HP, learning_rate=LR), "rows": []}
-med = statistics.median
-bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)  # noqa: E731
+       "steps_per_repeat": args.inner, "libmrp_sha256": lib_sha256(), "hyperparameters": dict(HP, learning_rate=LR), "rows": []}
+timed = lambda fn: device_ms(fn, args.inner, args.warmup, args.repeats, dev)  # noqa: E731
 for name, shared, pi, vf in ARCHS:
-    params = make_params(shared, pi, vf, seed=len(name))
+    params = bench_params(shared, pi, vf, seed=len(name))
     # the fused step is the rule, bitwise, on one minibatch
     small = make_batch(params, 128, seed=2)
     pol = P.DevicePolicy.from_params(params)
@@ -178,7 +137,7 @@ for name, shared, pi, vf in ARCHS:
             ppo.step(*batch, stats_out=st)
 
         tstep = torch_stepper(params, batch)
-        f_ms, t_ms = device_ms(fused), device_ms(tstep)
+        f_ms, t_ms = timed(fused), timed(tstep)
         spread = max(max(f_ms) - min(f_ms), max(t_ms) - min(t_ms))
         res["rows"].append({"arch": name, "batch": B, "n_params": ppo.n_params, "ms": {"step": med(f_ms), "torch_step": med(t_ms)},
                             "ms_min_max": {"step": [min(f_ms), max(f_ms)], "torch_step": [min(t_ms), max(t_ms)]},
@@ -186,8 +145,4 @@ for name, shared, pi, vf in ARCHS:
                             "step_ahead_by_more_than_the_spread": bool(med(t_ms) - med(f_ms) > spread)})
         ppo.close()
         pol.close()
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)

@@ -22,10 +22,8 @@ the tool asserts that both dist paths equal plain train() bitwise on a small buf
 Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -34,12 +32,11 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
+from trainbench import ACT, ARCHS, OBS, bench_params, bits, fill_buffer, lib_sha256, summary, write_json  # noqa: E402
 
 from gym_puzzles_amd import policy as P  # noqa: E402
 from gym_puzzles_amd import ppo as R  # noqa: E402
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
 from gym_puzzles_amd.dist import GradExchange, Shard  # noqa: E402
-from gym_puzzles_amd.rollout import DeviceRolloutBuffer  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=25)
@@ -52,10 +49,8 @@ if args.repeats < 20:
 if not torch.cuda.is_available():
     sys.exit("ppodistbench: no HIP device visible; nothing measured")
 
-OBS, ACT = 28, 6
 BATCHES = (128, 4096)
 BUFFERS = ((6, 4096), (128, 4096))
-ARCHS = (("sb3_default_pi64x2_vf64x2", [], [64, 64], [64, 64]), ("reference_shared256x2", [256, 256], [], []))
 HP = dict(clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5)
 CASES = ("plain", "copy", "collective")
 dev = torch.device("cuda", 0)
@@ -63,43 +58,6 @@ torch.cuda.set_device(dev)
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
 os.environ.setdefault("MASTER_PORT", "29517")
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
-bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)  # noqa: E731
-
-
-def make_params(shared, pi, vf, seed):
-    rng = np.random.default_rng(seed)
-
-    def tower(k, widths):
-        out = []
-        for n in widths:
-            out.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32)))
-            k = n
-        return out, k
-    s, kt = tower(OBS, shared)
-    p, kp = tower(kt, pi)
-    v, kv = tower(kt, vf)
-    (a,), _ = tower(kp, [ACT])
-    (c,), _ = tower(kv, [1])
-    return P.PolicyParams(s, p, v, a, c, np.linspace(-0.5, 0.0, ACT).astype(np.float32), "tanh")
-
-
-def fill_buffer(params, T, N, seed):
-    """A full buffer of plausible samples: the policy's own actions, values and log-probs."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    buf = DeviceRolloutBuffer(T, N, (OBS,), ACT, device=dev)
-    pol = P.DevicePolicy.from_params(params)
-    buf.observations.copy_(torch.randn(T, N, OBS, generator=g))
-    for t in range(T):
-        a, _, v, lp = pol.act(buf.observations[t].contiguous(), eps=torch.randn(N, ACT, generator=g).to(dev))
-        buf.actions[t].copy_(a)
-        buf.values[t].copy_(v)
-        buf.log_probs[t].copy_(lp)
-    buf.advantages.copy_(torch.randn(T, N, generator=g))
-    buf.returns.copy_(buf.values + torch.randn(T, N, generator=g).to(dev))
-    buf.pos, buf.full = T, True
-    torch.cuda.synchronize(dev)
-    pol.close()
-    return buf
 
 
 def make_ppo(params, case, B, lr):
@@ -109,7 +67,7 @@ def make_ppo(params, case, B, lr):
 
 
 def self_check(params):
-    buf = fill_buffer(params, 5, 60, seed=4)
+    buf = fill_buffer(params, 5, 60, seed=4, dev=dev)
     runs = []
     for case in CASES:
         pol, ppo = make_ppo(params, case, 128, 3e-4)
@@ -128,23 +86,19 @@ def one_call(ppo, buf, gen, n_minibatches):
     return (time.perf_counter() - t0) * 1e3 / n_minibatches
 
 
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
 res = {"device": torch.cuda.get_device_name(dev), "obs_dim": OBS, "act_dim": ACT, "repeats": args.repeats, "warmup": args.warmup,
-       "libmrp_sha256": sha, "hyperparameters": dict(HP, learning_rate=0.0, normalize_advantage=True, n_epochs=1),
+       "libmrp_sha256": lib_sha256(), "hyperparameters": dict(HP, learning_rate=0.0, normalize_advantage=True, n_epochs=1),
        "backend": "nccl (RCCL) at world size 1; the collective case forces all_gather_into_tensor on device tensors",
        "not_measured": "no multi-rank RCCL exchange over xGMI has run", "rows": []}
-med = statistics.median
-summary = lambda xs: {"median": med(xs), "min_max": [min(xs), max(xs)]}  # noqa: E731
 for name, shared, pi, vf in ARCHS:
-    params = make_params(shared, pi, vf, seed=len(name))
+    params = bench_params(shared, pi, vf, seed=len(name))
     same = self_check(params)
     assert same, f"{name}: train() through the exchange differs from plain train()"
     for T, N in BUFFERS:
         for B in BATCHES:
             rows = min(T, max(1, args.max_minibatches * B // N))
             n_mb = -(-rows * N // B)
-            buf = fill_buffer(params, rows, N, seed=3)
+            buf = fill_buffer(params, rows, N, seed=3, dev=dev)
             objs = {case: make_ppo(params, case, B, 0.0) for case in CASES}
             gens = {case: torch.Generator(device="cpu").manual_seed(7) for case in CASES}
             for _ in range(args.warmup):
@@ -167,8 +121,4 @@ for name, shared, pi, vf in ARCHS:
             res["rows"].append(row)
             print(json.dumps(row), flush=True)
 dist.destroy_process_group()
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)

@@ -26,10 +26,8 @@ bitwise on a small buffer: parameters, std and statistics.
 Needs a HIP device: without one nothing is timed and no file is written.
 """
 import argparse
-import hashlib
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -37,11 +35,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from trainbench import ACT, ARCHS, OBS, bench_params, bits, fill_buffer, lib_sha256, summary, write_json  # noqa: E402
 
 from gym_puzzles_amd import policy as P  # noqa: E402
 from gym_puzzles_amd import ppo as R  # noqa: E402
-from gym_puzzles_amd._native import LIB_PATH  # noqa: E402
-from gym_puzzles_amd.rollout import DeviceRolloutBuffer  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=25)
@@ -54,54 +51,15 @@ if args.repeats < 20:
 if not torch.cuda.is_available():
     sys.exit("ppotrainbench: no HIP device visible; nothing measured")
 
-OBS, ACT = 28, 6
 BATCHES = (128, 4096)
 BUFFERS = ((6, 4096), (128, 4096))          # n_steps x n_lanes: the reference config's rollout, and a long one
-ARCHS = (("sb3_default_pi64x2_vf64x2", [], [64, 64], [64, 64]), ("reference_shared256x2", [256, 256], [], []))
 HP = dict(clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5)
 dev = torch.device("cuda", 0)
-bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)  # noqa: E731
-
-
-def make_params(shared, pi, vf, seed):
-    rng = np.random.default_rng(seed)
-
-    def tower(k, widths):
-        out = []
-        for n in widths:
-            out.append(((rng.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32), (rng.standard_normal(n) * 0.1).astype(np.float32)))
-            k = n
-        return out, k
-    s, kt = tower(OBS, shared)
-    p, kp = tower(kt, pi)
-    v, kv = tower(kt, vf)
-    (a,), _ = tower(kp, [ACT])
-    (c,), _ = tower(kv, [1])
-    return P.PolicyParams(s, p, v, a, c, np.linspace(-0.5, 0.0, ACT).astype(np.float32), "tanh")
-
-
-def fill_buffer(params, T, N, seed, lp_shift=0.0):
-    """A full buffer of plausible samples: the policy's own actions, values and log-probs (plus lp_shift)."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    buf = DeviceRolloutBuffer(T, N, (OBS,), ACT, device=dev)
-    pol = P.DevicePolicy.from_params(params)
-    buf.observations.copy_(torch.randn(T, N, OBS, generator=g))
-    for t in range(T):
-        a, _, v, lp = pol.act(buf.observations[t].contiguous(), eps=torch.randn(N, ACT, generator=g).to(dev))
-        buf.actions[t].copy_(a)
-        buf.values[t].copy_(v)
-        buf.log_probs[t].copy_(lp + lp_shift)
-    buf.advantages.copy_(torch.randn(T, N, generator=g))
-    buf.returns.copy_(buf.values + torch.randn(T, N, generator=g).to(dev))
-    buf.pos, buf.full = T, True
-    torch.cuda.synchronize(dev)
-    pol.close()
-    return buf
 
 
 def self_check(params):
     T, N, bs = 5, 60, 128
-    buf = fill_buffer(params, T, N, seed=4)
+    buf = fill_buffer(params, T, N, seed=4, dev=dev)
     pol = P.DevicePolicy.from_params(params)
     ppo = R.DevicePPO(pol, learning_rate=3e-4, n_epochs=2, batch_size=bs, normalize_advantage=True, minibatch="device", **HP)
     stats = ppo.train(buf, generator=torch.Generator(device="cpu").manual_seed(1)).cpu().numpy()
@@ -140,16 +98,12 @@ def timed(ppo, buf, n_minibatches):
     return dev_ms, wall_ms
 
 
-with open(os.environ.get("MRP_LIB") or LIB_PATH, "rb") as f:
-    sha = hashlib.sha256(f.read()).hexdigest()
 res = {"device": torch.cuda.get_device_name(dev), "obs_dim": OBS, "act_dim": ACT, "repeats": args.repeats, "warmup": args.warmup,
-       "libmrp_sha256": sha, "hyperparameters": dict(HP, learning_rate=0.0, normalize_advantage=True, n_epochs=1),
+       "libmrp_sha256": lib_sha256(), "hyperparameters": dict(HP, learning_rate=0.0, normalize_advantage=True, n_epochs=1),
        "baseline": 'minibatch="torch" with no option set runs the code path train() had before the device gather existed',
        "rows": []}
-med = statistics.median
-summary = lambda xs: {"median": med(xs), "min_max": [min(xs), max(xs)]}  # noqa: E731
 for name, shared, pi, vf in ARCHS:
-    params = make_params(shared, pi, vf, seed=len(name))
+    params = bench_params(shared, pi, vf, seed=len(name))
     same = self_check(params)
     assert same, f'{name}: train(minibatch="device") differs from ppo_train_ref'
     for T, N in BUFFERS:
@@ -157,8 +111,8 @@ for name, shared, pi, vf in ARCHS:
             # cut the buffer's rows so that a timed call holds at most --max-minibatches minibatches
             rows = min(T, max(1, args.max_minibatches * B // N))
             n_mb = -(-rows * N // B)
-            buf = fill_buffer(params, rows, N, seed=3)
-            far = fill_buffer(params, rows, N, seed=3, lp_shift=0.5)
+            buf = fill_buffer(params, rows, N, seed=3, dev=dev)
+            far = fill_buffer(params, rows, N, seed=3, dev=dev, lp_shift=0.5)
             row = {"arch": name, "buffer": [T, N], "rows_timed": rows, "batch": B, "minibatches_per_call": n_mb,
                    "device_equals_ppo_train_ref": same}
             for key, mode, kl, b in (("torch", "torch", None, buf), ("device", "device", None, buf), ("skipped", "device", 0.0, far)):
@@ -177,8 +131,4 @@ for name, shared, pi, vf in ARCHS:
             row["device_ahead_by_more_than_the_spread"] = bool(t["wall_ms_per_minibatch"]["median"] - d["wall_ms_per_minibatch"]["median"] > spread)
             res["rows"].append(row)
             print(json.dumps(row), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write_json(res, args.out)
